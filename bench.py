@@ -1,8 +1,17 @@
 """Benchmark: Msamples/s on cornell_box 1920x1080, 256 spp, 8 bounces (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c4|c5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
     python bench.py --gpus N --single-process      # N devices behind one pt_renderer_create_multi
+
+A plain run sets up, renders W warm-up frames, times K frames and prints the
+result line: the headline figure and what describes the run (workload, tile
+deal, gather, topology, tuning), nothing that needs a frame or a CPU run of
+its own.  --dump-outputs DIR writes the last timed step's frame to
+DIR/frame.npy (float64, one row of r, g, b per pixel, row-major; a frame above
+the size cap is written as a fixed seeded sample of its pixels, their indices
+in DIR/frame_pixels.npy).  --full adds the roofline, parity and CPU-baseline
+sections described below.
 
 A plain `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment)
 starts `python -m torch.distributed.run --nproc-per-node N ... bench.py ...`
@@ -20,7 +29,7 @@ each rank renders its tiles into a compact shard, the shards are gathered to
 rank 0 over RCCL (torch.distributed "nccl") and un-interleaved there: the same
 frame at every N ("scaling": "strong").  Rank 0 prints one JSON line.
 
-After the timed steps (not part of `value`):
+With --full, after the timed steps (not part of `value`):
 * roofline: one more frame with one chunk stream (wf_slots = 1), so every
   render kernel runs alone and its HIP-event launch durations are its own; the
   dominant kernel's algorithmic FLOPs per launch / its mean launch duration.
@@ -137,6 +146,11 @@ def parse():
     ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl",
                     help="ranks' process group: nccl (= RCCL, the multi-GPU default) or gloo (rehearsal: shards "
                          "gathered through host memory, ranks may share a GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's frame to DIR/frame.npy (float64 [pixels, 3])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: per-kernel timing frame, one-stream roofline frame, FLOP "
+                         "counters, parity against the oracle, CPU baseline (each can be switched off below)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target length of each CPU-baseline run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
@@ -146,6 +160,8 @@ def parse():
     ap.add_argument("--parity-pixels", type=int, default=0,
                     help="0: the stratified set (>= 8192 pixels); n: n random pixels")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the mean over the timed steps)")
     if a.config:
         a.scene, a.width, a.height, a.spp = CONFIGS[a.config]
     return a
@@ -380,6 +396,29 @@ def pmc_lookup(what, scene, depth, width, height, spp, source, root=ROOT):
     return f, rec, spf, None
 
 
+DUMP_CAP_BYTES = 48 << 20  # --dump-outputs: the files of one run stay below this in all (C2's whole frame does)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(out_dir, img):
+    """Writes the frame a caller of the timed path receives (img: float64 [W*H, 3], row-major pixels) to
+    out_dir/frame.npy.  A frame above DUMP_CAP_BYTES is written as a sample of its pixels instead: the same sorted
+    pixel indices for the same frame size in every run (a seeded draw), stored beside it in frame_pixels.npy
+    (float64: exact for any pixel index)."""
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    img = np.ascontiguousarray(img, dtype=np.float64)
+    if img.nbytes <= DUMP_CAP_BYTES:
+        np.save(d / "frame.npy", img)
+        return {"frame": list(img.shape)}
+    n = DUMP_CAP_BYTES // (4 * 8)  # three channels and the index, 8 bytes each, per sampled pixel
+    px = np.sort(np.random.default_rng(DUMP_SEED).choice(img.shape[0], size=n, replace=False))
+    np.save(d / "frame.npy", img[px])
+    np.save(d / "frame_pixels.npy", px.astype(np.float64))
+    return {"frame": [int(n), 3], "frame_pixels": [int(n)], "of_pixels": int(img.shape[0])}
+
+
 def main():
     args = parse()
     if launch_plan(args, os.environ) == "spawn":
@@ -513,7 +552,7 @@ def main():
     # per-kernel launch durations: one more frame of the same workload with HIP events around every launch, after
     # the timed region (the events' marker packets would add gaps between a small frame's ~50 dependent launches)
     kt = {}
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         pt.kernel_timing(r, True)
         step()
         torch.cuda.synchronize()
@@ -527,7 +566,7 @@ def main():
 
     # roofline leg: one frame with every render kernel alone on the device (one chunk stream)
     kt_iso = None
-    if not args.no_roofline_leg:
+    if args.full and not args.no_roofline_leg:
         r.set_option("wf_slots", 1)
         pt.kernel_timing(r, True)
         if multi:
@@ -543,62 +582,7 @@ def main():
         value = samples_frame * args.steps / elapsed / 1e6
         sys.path.insert(0, str(ROOT / "oracle"))
 
-        # roofline of the dominant kernel (this rank's / the first device's launches)
-        F, counts = algorithmic_flops(pt, r, cam, args)
-        share = 1.0 if multi else pt.shard_tiles(W, H, rank, world) / pt.shard_tiles(W, H, 0, 1)
-        if multi:  # kernel timing covers the first device: its tile share
-            share = pt.shard_tiles(W, H, 0, args.gpus) / pt.shard_tiles(W, H, 0, 1)
-        samples_share = samples_frame * share
-        src = kt_iso if kt_iso is not None else kt  # each one frame
-        if not src:  # neither timing frame ran (--no-roofline-leg --no-kernel-timing: profiler passes)
-            src = {"bounce": (float("nan"), 1)}
-        nfr = 1
-        walked = node_kernel(src) == "walk"  # the trace runs in wf_walk (large tree, no marched shape)
-        bounce_ev = [k for k in FLOP_WEIGHTS if k not in MARCH_EVENTS and not (walked and k in WALK_EVENTS)]
-        f_weights = {"march": flops_per_sample(counts, MARCH_EVENTS),
-                     "bounce": flops_per_sample(counts, bounce_ev),
-                     "walk": flops_per_sample(counts, WALK_EVENTS) if walked else 0.0,
-                     "megakernel": F}
         workload = "%s %dx%d %dspp depth %d" % (args.scene, W, H, spp, args.depth)
-        # algorithmic FLOPs per sample: from the f64 instruction counters of a committed PMC pass of this
-        # workload (scripts/pmc_flops.py) when there is one, else the event counts times FLOP_WEIGHTS
-        src_id = pt.source_id()
-        ff, fl, _, f_why = pmc_lookup("flops", args.scene, args.depth, W, H, spp, src_id)
-        f_kind = dict(f_weights)
-        if fl:
-            for k, v in fl["kinds"].items():
-                f_kind[k] = v["algorithmic_flops_per_sample"]
-            F = f_kind["bounce"] + f_kind["march"] + f_kind.get("walk", 0.0)
-        kname = {"bounce": "wf_bounce", "march": "wf_march", "walk": "wf_walk", "megakernel": "render_tiles"}
-        dom = max(("bounce", "march", "walk", "megakernel"), key=lambda k: src.get(k, (0, 0))[0])
-        dom_ms, dom_n = src[dom]
-        achieved = f_kind[dom] * samples_share * nfr / (dom_ms / 1e3) / 1e12
-        per_kernel = {}
-        for k in ("bounce", "march", "walk", "megakernel"):
-            ms_k, n_k = src.get(k, (0.0, 0))
-            if n_k:
-                a_k = f_kind[k] * samples_share * nfr / (ms_k / 1e3) / 1e12
-                per_kernel[kname[k]] = {"achieved": round(a_k, 4), "frac": round(a_k / FP64_PEAK_TFLOPS, 5),
-                                        "flops_per_sample": round(f_kind[k], 1),
-                                        "flops_per_sample_weights": round(f_weights[k], 1), "launches": n_k // nfr,
-                                        "ms_per_frame": round(ms_k / nfr, 3),
-                                        "kernel_ms_avg": round(ms_k / n_k, 4)}
-        # the large-tree bounce build tests BVH nodes in f32: 6 FMAs per node slab, outside the f64
-        # counters; reported beside the f64 roofline, and both shares of the VALU's FLOP rate summed
-        f32_kind = {}
-        nk = node_kernel(src)
-        if r.get_option("bvh_nodes") >= BIG_BVH_NODES and src.get(nk, (0, 0))[1] > 0:
-            f32_ps = f32_node_flops_per_sample(counts)
-            ms_b, _ = src[nk]
-            a32 = f32_ps * samples_share * nfr / (ms_b / 1e3) / 1e12
-            f32_kind = {"kernel": kname[nk], "flops_per_sample": round(f32_ps, 1), "achieved": round(a32, 4),
-                        "peak": FP32_PEAK_TFLOPS, "frac": round(a32 / FP32_PEAK_TFLOPS, 5),
-                        "source": "(node_slabs - bounces) events (pt_count_work) x 12: six f32 FMAs per node, "
-                                  "less the root test the large-tree walk skips once per trace"}
-            if kname[nk] in per_kernel:
-                per_kernel[kname[nk]]["valu_frac_f64_plus_f32"] = round(
-                    per_kernel[kname[nk]]["frac"] + a32 / FP32_PEAK_TFLOPS, 5)
-        out_bytes = 24.0 * W * H * share
         tuning = {k: v for k, v in r.options().items() if v != pt.OPTION_DEFAULTS.get(k)}
         rec = {
             "metric": metric_name(args), "value": round(value, 3), "unit": "Msamples/s", "n_gpus": n_gpus,
@@ -612,43 +596,7 @@ def main():
                                        "GPU(s))" % (world, torch.cuda.device_count()) if gloo else
                                        "tile-interleaved x%d, RCCL gather" % world if world > 1 else "single GPU"),
                        "wf_slots": slots},
-            "roofline": {"bound": "valu_f64", "achieved": round(achieved, 4), "peak": FP64_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(achieved / FP64_PEAK_TFLOPS, 5), "traffic": None,
-                         "kernel": kname[dom], "flops_per_sample": round(f_kind[dom], 1),
-                         "launches": dom_n // nfr, "kernel_ms_avg": round(dom_ms / max(1, dom_n), 4),
-                         "measured": ("one extra frame after the timed steps with one chunk stream (wf_slots=1): "
-                                      "every launch alone on the device, HIP events on its stream"
-                                      if kt_iso is not None else "timed steps (launches of two chunk streams overlap)"),
-                         "kernels": per_kernel,
-                         "valu_f32": f32_kind or None,
-                         "flops_per_sample_total": round(F, 1),
-                         "flops_source": ("f64 instruction counters x mean active lanes, %s (%s; scripts/pmc_flops.py); "
-                                          "event weights give %.1f FLOP/sample (%.2fx)"
-                                          % (ff.relative_to(ROOT), fl["workload"],
-                                             f_weights["bounce"] + f_weights["march"] + f_weights["walk"],
-                                             (f_weights["bounce"] + f_weights["march"] + f_weights["walk"]) / F)
-                                          if fl else
-                                          "kernel event counters (pt_count_work) x FLOP_WEIGHTS (%s)" % f_why),
-                         "events_per_sample": {k: round(v / max(1, counts["samples"]), 3)
-                                               for k, v in counts.items() if k != "samples"},
-                         # the timed steps: two chunk streams run concurrently (pt_wave.hip), so one kernel's
-                         # launches overlap the other stream's; these sums of launch durations can exceed the
-                         # step time, and the whole path's rate is the frame's FLOPs over the frame time
-                         "kernel_ms_per_step_summed_over_streams": {k: round(v[0], 3) for k, v in kt.items()} or None,
-                         "kernel_ms_note": ("one frame of the timed workload after the timed steps, HIP events "
-                                            "around each launch; launch durations summed per kernel kind over %d "
-                                            "concurrent chunk streams: they overlap, so a sum may exceed "
-                                            "ms_per_step; per-kernel times of launches that run alone are in "
-                                            "`kernels`" % slots),
-                         "frame_kernels_ms": round(kernel_ms, 3), "frame_kernels_ms_max_rank": round(kernel_ms_max, 3),
-                         "path_achieved": round(F * value * 1e6 / 1e12, 4),
-                         "path_frac": round(F * value * 1e6 / 1e12 / FP64_PEAK_TFLOPS, 5)},
-            "roofline_hbm": {"achieved": round(out_bytes / (kernel_ms / 1e3) / 1e9, 4), "peak": HBM_PEAK_GBS,
-                             "unit": "GB/s", "frac": out_bytes / (kernel_ms / 1e3) / 1e9 / HBM_PEAK_GBS,
-                             "bytes_per_launch": out_bytes, "note": "algorithmic: 24 B/pixel frame write"},
             "march_guard_drops": guard_drops,
-            "frame_plan": {"chunks_per_frame": kt["reduce"][1] if kt else None, "chunk_streams": slots,
-                           "note": "the timed frames' sample chunks (one wf_reduce each) on this rank / first device"},
         }
         per_rank_tiles = [pt.shard_tiles(W, H, k, n_gpus) for k in range(n_gpus)]
         rec["rank_share"] = {"tiles_total": pt.shard_tiles(W, H, 0, 1), "tiles_per_rank_max": max(per_rank_tiles),
@@ -672,47 +620,148 @@ def main():
                              "what": "hipMemcpyPeerAsync of each device's shard to the first device, per band"}
         if tuning:
             rec["tuning"] = tuning
-        # roofline.traffic: HBM bytes per launch of the same kernel from the committed PMC passes of this
-        # workload (scripts/pmc_traffic.py; bench.py cannot read PMC counters itself)
-        tf, tr, t_spf, t_why = pmc_lookup("traffic", args.scene, args.depth, W, H, spp, src_id)
-        if not tr:
-            rec["roofline"]["traffic_source"] = t_why
-        kind = tr.get("kinds", {}).get(dom) if tr else None
-        if kind:
-            # bytes per sample of the pass (its launches x bytes per launch over its samples), times the samples
-            # this rank's (or first device's) launches of the kernel processed, per launch: bytes per sample do
-            # not depend on the chunking or the frame size, bytes per launch do
-            per_sample = kind["traffic"] * kind["launches"] / (t_spf * tr.get("frames", 1))
-            per_launch = per_sample * samples_share * nfr / max(1, dom_n)
-            rec["roofline"]["traffic"] = round(per_launch)
-            rec["roofline"]["traffic_source"] = ("%s (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, %s)"
-                                                 % (tf.relative_to(ROOT), tr["workload"]))
-            rec["roofline"]["traffic_gbs"] = round(per_launch / (dom_ms / max(1, dom_n) / 1e3) / 1e9, 1)
-            rec["roofline"]["traffic_per_sample"] = round(per_sample, 1)
-            if world > 1 or multi:
-                rec["roofline"]["traffic_note"] = "per launch of this rank's share (%d of %d tiles)" % (
-                    per_rank_tiles[0], pt.shard_tiles(W, H, 0, 1))
-        if not args.no_parity:
-            import oracle
-            px = parity_pixels(args)
-            sc = oracle.Scene(text, seed=args.scene_seed).use_bvh(True, 7)
-            t = time.perf_counter()
-            ref = sc.render(W, H, spp, args.depth, args.seed, pixels=px, threads=host_cpus()["share"])
-            got = img[px]
-            rec["rms_vs_oracle"] = float(np.sqrt(np.mean((got - ref) ** 2)))
-            rec["rms_per_channel"] = [float(x) for x in np.sqrt(np.mean((got - ref) ** 2, axis=0))]
-            rec["rms_pixels"] = int(len(px))
-            rec["exact_pixels_frac"] = float(np.mean(np.all(got == ref, axis=1)))
-            rec["parity_pixels"] = ("stratified: 16-px grid + full row %d + full column %d, %d spp, %.1f s"
-                                    % (min(H - 1, H * 757 // 1080), min(W - 1, W * 1142 // 1920), spp,
-                                       time.perf_counter() - t) if not args.parity_pixels
-                                    else "%d random pixels" % len(px))
-            rec["parity_frame"] = ("the last timed step's frame (the one behind `value`: %d chunks on %d chunk "
-                                   "streams%s), copied out before the kernel-timing and roofline frames"
-                                   % (rec["frame_plan"]["chunks_per_frame"], slots,
-                                      ", gathered from %d ranks" % world if world > 1 else ""))
-        if world == 1 and not args.no_cpu_baseline:
-            rec["cpu_baseline"] = cpu_baseline(text, args)
+        if args.dump_outputs:
+            rec["outputs"] = {"dir": args.dump_outputs, "what": "the last timed step's frame, float64 rgb per "
+                              "pixel", "arrays": dump_outputs(args.dump_outputs, img)}
+        if args.full:  # the sections that take frames, counter runs or CPU runs of their own
+            # roofline of the dominant kernel (this rank's / the first device's launches)
+            F, counts = algorithmic_flops(pt, r, cam, args)
+            share = 1.0 if multi else pt.shard_tiles(W, H, rank, world) / pt.shard_tiles(W, H, 0, 1)
+            if multi:  # kernel timing covers the first device: its tile share
+                share = pt.shard_tiles(W, H, 0, args.gpus) / pt.shard_tiles(W, H, 0, 1)
+            samples_share = samples_frame * share
+            src = kt_iso if kt_iso is not None else kt  # each one frame
+            if not src:  # neither timing frame ran (--no-roofline-leg --no-kernel-timing: profiler passes)
+                src = {"bounce": (float("nan"), 1)}
+            nfr = 1
+            walked = node_kernel(src) == "walk"  # the trace runs in wf_walk (large tree, no marched shape)
+            bounce_ev = [k for k in FLOP_WEIGHTS if k not in MARCH_EVENTS and not (walked and k in WALK_EVENTS)]
+            f_weights = {"march": flops_per_sample(counts, MARCH_EVENTS),
+                         "bounce": flops_per_sample(counts, bounce_ev),
+                         "walk": flops_per_sample(counts, WALK_EVENTS) if walked else 0.0,
+                         "megakernel": F}
+            # algorithmic FLOPs per sample: from the f64 instruction counters of a committed PMC pass of this
+            # workload (scripts/pmc_flops.py) when there is one, else the event counts times FLOP_WEIGHTS
+            src_id = pt.source_id()
+            ff, fl, _, f_why = pmc_lookup("flops", args.scene, args.depth, W, H, spp, src_id)
+            f_kind = dict(f_weights)
+            if fl:
+                for k, v in fl["kinds"].items():
+                    f_kind[k] = v["algorithmic_flops_per_sample"]
+                F = f_kind["bounce"] + f_kind["march"] + f_kind.get("walk", 0.0)
+            kname = {"bounce": "wf_bounce", "march": "wf_march", "walk": "wf_walk", "megakernel": "render_tiles"}
+            dom = max(("bounce", "march", "walk", "megakernel"), key=lambda k: src.get(k, (0, 0))[0])
+            dom_ms, dom_n = src[dom]
+            achieved = f_kind[dom] * samples_share * nfr / (dom_ms / 1e3) / 1e12
+            per_kernel = {}
+            for k in ("bounce", "march", "walk", "megakernel"):
+                ms_k, n_k = src.get(k, (0.0, 0))
+                if n_k:
+                    a_k = f_kind[k] * samples_share * nfr / (ms_k / 1e3) / 1e12
+                    per_kernel[kname[k]] = {"achieved": round(a_k, 4), "frac": round(a_k / FP64_PEAK_TFLOPS, 5),
+                                            "flops_per_sample": round(f_kind[k], 1),
+                                            "flops_per_sample_weights": round(f_weights[k], 1), "launches": n_k // nfr,
+                                            "ms_per_frame": round(ms_k / nfr, 3),
+                                            "kernel_ms_avg": round(ms_k / n_k, 4)}
+            # the large-tree bounce build tests BVH nodes in f32: 6 FMAs per node slab, outside the f64
+            # counters; reported beside the f64 roofline, and both shares of the VALU's FLOP rate summed
+            f32_kind = {}
+            nk = node_kernel(src)
+            if r.get_option("bvh_nodes") >= BIG_BVH_NODES and src.get(nk, (0, 0))[1] > 0:
+                f32_ps = f32_node_flops_per_sample(counts)
+                ms_b, _ = src[nk]
+                a32 = f32_ps * samples_share * nfr / (ms_b / 1e3) / 1e12
+                f32_kind = {"kernel": kname[nk], "flops_per_sample": round(f32_ps, 1), "achieved": round(a32, 4),
+                            "peak": FP32_PEAK_TFLOPS, "frac": round(a32 / FP32_PEAK_TFLOPS, 5),
+                            "source": "(node_slabs - bounces) events (pt_count_work) x 12: six f32 FMAs per node, "
+                                      "less the root test the large-tree walk skips once per trace"}
+                if kname[nk] in per_kernel:
+                    per_kernel[kname[nk]]["valu_frac_f64_plus_f32"] = round(
+                        per_kernel[kname[nk]]["frac"] + a32 / FP32_PEAK_TFLOPS, 5)
+            out_bytes = 24.0 * W * H * share
+            rec.update({
+                "roofline": {"bound": "valu_f64", "achieved": round(achieved, 4), "peak": FP64_PEAK_TFLOPS,
+                             "unit": "TFLOP/s", "frac": round(achieved / FP64_PEAK_TFLOPS, 5), "traffic": None,
+                             "kernel": kname[dom], "flops_per_sample": round(f_kind[dom], 1),
+                             "launches": dom_n // nfr, "kernel_ms_avg": round(dom_ms / max(1, dom_n), 4),
+                             "measured": ("one extra frame after the timed steps with one chunk stream (wf_slots=1): "
+                                          "every launch alone on the device, HIP events on its stream"
+                                          if kt_iso is not None else
+                                          "timed steps (launches of two chunk streams overlap)"),
+                             "kernels": per_kernel,
+                             "valu_f32": f32_kind or None,
+                             "flops_per_sample_total": round(F, 1),
+                             "flops_source": ("f64 instruction counters x mean active lanes, %s (%s; "
+                                              "scripts/pmc_flops.py); event weights give %.1f FLOP/sample (%.2fx)"
+                                              % (ff.relative_to(ROOT), fl["workload"],
+                                                 f_weights["bounce"] + f_weights["march"] + f_weights["walk"],
+                                                 (f_weights["bounce"] + f_weights["march"] + f_weights["walk"]) / F)
+                                              if fl else
+                                              "kernel event counters (pt_count_work) x FLOP_WEIGHTS (%s)" % f_why),
+                             "events_per_sample": {k: round(v / max(1, counts["samples"]), 3)
+                                                   for k, v in counts.items() if k != "samples"},
+                             # the timed steps: two chunk streams run concurrently (pt_wave.hip), so one kernel's
+                             # launches overlap the other stream's; these sums of launch durations can exceed the
+                             # step time, and the whole path's rate is the frame's FLOPs over the frame time
+                             "kernel_ms_per_step_summed_over_streams": ({k: round(v[0], 3) for k, v in kt.items()}
+                                                                        or None),
+                             "kernel_ms_note": ("one frame of the timed workload after the timed steps, HIP events "
+                                                "around each launch; launch durations summed per kernel kind over %d "
+                                                "concurrent chunk streams: they overlap, so a sum may exceed "
+                                                "ms_per_step; per-kernel times of launches that run alone are in "
+                                                "`kernels`" % slots),
+                             "frame_kernels_ms": round(kernel_ms, 3),
+                             "frame_kernels_ms_max_rank": round(kernel_ms_max, 3),
+                             "path_achieved": round(F * value * 1e6 / 1e12, 4),
+                             "path_frac": round(F * value * 1e6 / 1e12 / FP64_PEAK_TFLOPS, 5)},
+                "roofline_hbm": {"achieved": round(out_bytes / (kernel_ms / 1e3) / 1e9, 4), "peak": HBM_PEAK_GBS,
+                                 "unit": "GB/s", "frac": out_bytes / (kernel_ms / 1e3) / 1e9 / HBM_PEAK_GBS,
+                                 "bytes_per_launch": out_bytes, "note": "algorithmic: 24 B/pixel frame write"},
+                "frame_plan": {"chunks_per_frame": kt["reduce"][1] if kt else None, "chunk_streams": slots,
+                               "note": "the timed frames' sample chunks (one wf_reduce each) on this rank / first "
+                                       "device"},
+            })
+            # roofline.traffic: HBM bytes per launch of the same kernel from the committed PMC passes of this
+            # workload (scripts/pmc_traffic.py; bench.py cannot read PMC counters itself)
+            tf, tr, t_spf, t_why = pmc_lookup("traffic", args.scene, args.depth, W, H, spp, src_id)
+            if not tr:
+                rec["roofline"]["traffic_source"] = t_why
+            kind = tr.get("kinds", {}).get(dom) if tr else None
+            if kind:
+                # bytes per sample of the pass (its launches x bytes per launch over its samples), times the samples
+                # this rank's (or first device's) launches of the kernel processed, per launch: bytes per sample do
+                # not depend on the chunking or the frame size, bytes per launch do
+                per_sample = kind["traffic"] * kind["launches"] / (t_spf * tr.get("frames", 1))
+                per_launch = per_sample * samples_share * nfr / max(1, dom_n)
+                rec["roofline"]["traffic"] = round(per_launch)
+                rec["roofline"]["traffic_source"] = ("%s (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, %s)"
+                                                     % (tf.relative_to(ROOT), tr["workload"]))
+                rec["roofline"]["traffic_gbs"] = round(per_launch / (dom_ms / max(1, dom_n) / 1e3) / 1e9, 1)
+                rec["roofline"]["traffic_per_sample"] = round(per_sample, 1)
+                if world > 1 or multi:
+                    rec["roofline"]["traffic_note"] = "per launch of this rank's share (%d of %d tiles)" % (
+                        per_rank_tiles[0], pt.shard_tiles(W, H, 0, 1))
+            if not args.no_parity:
+                import oracle
+                px = parity_pixels(args)
+                sc = oracle.Scene(text, seed=args.scene_seed).use_bvh(True, 7)
+                t = time.perf_counter()
+                ref = sc.render(W, H, spp, args.depth, args.seed, pixels=px, threads=host_cpus()["share"])
+                got = img[px]
+                rec["rms_vs_oracle"] = float(np.sqrt(np.mean((got - ref) ** 2)))
+                rec["rms_per_channel"] = [float(x) for x in np.sqrt(np.mean((got - ref) ** 2, axis=0))]
+                rec["rms_pixels"] = int(len(px))
+                rec["exact_pixels_frac"] = float(np.mean(np.all(got == ref, axis=1)))
+                rec["parity_pixels"] = ("stratified: 16-px grid + full row %d + full column %d, %d spp, %.1f s"
+                                        % (min(H - 1, H * 757 // 1080), min(W - 1, W * 1142 // 1920), spp,
+                                           time.perf_counter() - t) if not args.parity_pixels
+                                        else "%d random pixels" % len(px))
+                rec["parity_frame"] = ("the last timed step's frame (the one behind `value`: %d chunks on %d chunk "
+                                       "streams%s), copied out before the kernel-timing and roofline frames"
+                                       % (rec["frame_plan"]["chunks_per_frame"], slots,
+                                          ", gathered from %d ranks" % world if world > 1 else ""))
+            if world == 1 and not args.no_cpu_baseline:
+                rec["cpu_baseline"] = cpu_baseline(text, args)
         print(json.dumps(finite_or_null(rec)), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -11,7 +11,7 @@ for rep in $(seq 1 $reps); do
     for v in "$@"; do
         if [ "$v" = default ]; then lib=""; else lib=$R/variants/$v.so; fi
         echo "== $v rep $rep" >> $OUT/ab.log
-        PT_AMD_LIB=$lib timeout -k 10 300 python -u bench.py --no-cpu-baseline --parity-pixels 64 --steps 3 ${BENCH_ARGS} \
+        PT_AMD_LIB=$lib timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --parity-pixels 64 --steps 3 ${BENCH_ARGS} \
             >> $OUT/ab.log 2>&1
     done
 done

@@ -14,7 +14,7 @@ for rep in $(seq 1 $reps); do
         name=${v%%|*}; args=${v#*|}; [ "$args" = "-" ] && args=""
         if [ "$name" = default ]; then lib=""; else lib=$R/variants/$name.so; fi
         echo "== $name rep $rep :: $args" >> $OUT/ab.log
-        PT_AMD_LIB=$lib timeout -k 10 300 python -u bench.py --no-cpu-baseline --parity-pixels 64 --steps 3 $args \
+        PT_AMD_LIB=$lib timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --parity-pixels 64 --steps 3 $args \
             >> $OUT/ab.log 2>&1
     done
 done

@@ -11,7 +11,7 @@
 #        the JSONs name the build (source_id) so bench.py uses them only for that build,
 #        for any frame size and spp of the same scene and depth (c4 uses c2/c3's).
 # stall:  SQ wave-cycle split (active / memory wait / issue-stalled) of c2 and c5 one-stream frames.
-# bench: bench.py lines for c1, c2 (default), c3, c4, c5 with parity and CPU baseline, c2 and c1 at depth 50,
+# bench: bench.py --full lines for c1, c2 (default), c3, c4, c5 with parity and CPU baseline, c2 and c1 at depth 50,
 #        the interactive workload (scripts/interactive_bench.py),
 #        and c2 / c4 through 8 gloo ranks sharing the GPU (the multi-rank path).
 # kt:    rocprofv3 --kernel-trace --stats of the default bench (+ one-stream leg).
@@ -47,28 +47,28 @@ if [ "$what" = stall ] || [ "$what" = all ]; then
     done
 fi
 if [ "$what" = bench ] || [ "$what" = all ]; then
-    timeout -k 10 300 python -u bench.py --steps 5 --warmup 1 > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+    timeout -k 10 300 python -u bench.py --full --steps 5 --warmup 1 > $OUT/bench_c2.json 2> $OUT/bench_c2.err
     echo "bench c2 done" >> $OUT/progress.txt
-    timeout -k 10 300 python -u bench.py --config c1 --steps 20 --warmup 2 > $OUT/bench_c1.json 2> $OUT/bench_c1.err
-    timeout -k 10 600 python -u bench.py --config c3 --steps 2 --warmup 1 > $OUT/bench_c3.json 2> $OUT/bench_c3.err
+    timeout -k 10 300 python -u bench.py --full --config c1 --steps 20 --warmup 2 > $OUT/bench_c1.json 2> $OUT/bench_c1.err
+    timeout -k 10 600 python -u bench.py --full --config c3 --steps 2 --warmup 1 > $OUT/bench_c3.json 2> $OUT/bench_c3.err
     echo "bench c3 done" >> $OUT/progress.txt
-    timeout -k 10 600 python -u bench.py --config c5 --steps 3 --warmup 1 > $OUT/bench_c5.json 2> $OUT/bench_c5.err
+    timeout -k 10 600 python -u bench.py --full --config c5 --steps 3 --warmup 1 > $OUT/bench_c5.json 2> $OUT/bench_c5.err
     echo "bench c5 done" >> $OUT/progress.txt
     # the reference GUI's depth (informational: the configs are quoted at depth 8)
-    timeout -k 10 600 python -u bench.py --depth 50 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_c2_depth50.json \
+    timeout -k 10 600 python -u bench.py --full --depth 50 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_c2_depth50.json \
         2> $OUT/bench_c2_depth50.err
-    timeout -k 10 300 python -u bench.py --config c1 --depth 50 --steps 20 --warmup 2 --no-cpu-baseline \
+    timeout -k 10 300 python -u bench.py --full --config c1 --depth 50 --steps 20 --warmup 2 --no-cpu-baseline \
         > $OUT/bench_c1_depth50.json 2> $OUT/bench_c1_depth50.err
     timeout -k 10 300 python -u scripts/interactive_bench.py --out $OUT/interactive.jsonl > $OUT/interactive.log 2>&1
     echo "bench depth 50 + interactive done" >> $OUT/progress.txt
 fi
 if [ "$what" = bench4 ] || [ "$what" = all ]; then
-    timeout -k 10 900 python -u bench.py --config c4 --steps 1 --warmup 1 > $OUT/bench_c4.json 2> $OUT/bench_c4.err
+    timeout -k 10 900 python -u bench.py --full --config c4 --steps 1 --warmup 1 > $OUT/bench_c4.json 2> $OUT/bench_c4.err
     echo "bench c4 done" >> $OUT/progress.txt
     for c in c2 c4; do
         st=3; if [ $c = c4 ]; then st=1; fi
         timeout -k 10 900 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
-            --master-port 29517 bench.py --gpus 8 --dist-backend gloo --config $c --steps $st --warmup 1 \
+            --master-port 29517 bench.py --full --gpus 8 --dist-backend gloo --config $c --steps $st --warmup 1 \
             > $OUT/bench_${c}_gloo8.json 2> $OUT/bench_${c}_gloo8.err
         echo "bench $c gloo8 done" >> $OUT/progress.txt
     done
@@ -81,6 +81,6 @@ if [ "$what" = ranksim ]; then
     echo "ranksim c4 done" >> $OUT/progress.txt
 fi
 if [ "$what" = kt ] || [ "$what" = all ]; then
-    PROF_TIMEOUT=400 bash scripts/gpu.sh kt $tag/kt_default --no-cpu-baseline --no-parity --no-kernel-timing
+    PROF_TIMEOUT=400 bash scripts/gpu.sh kt $tag/kt_default --full --no-cpu-baseline --no-parity --no-kernel-timing
     echo "kt done" >> $OUT/progress.txt
 fi

@@ -6,7 +6,8 @@
 #   bash scripts/gpu.sh tests    <tag> [pytest -k expr]   GPU test suite
 #   bash scripts/gpu.sh smoke    <tag>                    __graft_entry__.smoke()
 #   bash scripts/gpu.sh bench    <tag> [bench args...]    one bench.py line -> <tag>/bench.log
-#   bench A/B of tuning knobs:   bash scripts/gpu.sh bench <tag> --no-cpu-baseline --option wf_slots=1
+#   (--full adds roofline, parity and CPU baseline to the line)
+#   bench A/B of tuning knobs:   bash scripts/gpu.sh bench <tag> --full --no-cpu-baseline --option wf_slots=1
 #   bash scripts/gpu.sh kt       <tag> [bench args...]    rocprofv3 --kernel-trace --stats of bench.py
 #   bash scripts/gpu.sh pmc      <tag> [bench args...]    FETCH_SIZE / WRITE_SIZE passes (separate runs)
 #                                                         -> <tag>/pmc_traffic.json (scripts/pmc_traffic.py)
@@ -68,8 +69,8 @@ list)
 evidence)
     bash scripts/gpu.sh tests $tag
     bash scripts/gpu.sh smoke $tag
-    bash scripts/gpu.sh bench $tag
-    bash scripts/gpu.sh kt $tag/kt_default --no-cpu-baseline --no-parity --no-kernel-timing
+    bash scripts/gpu.sh bench $tag --full
+    bash scripts/gpu.sh kt $tag/kt_default --full --no-cpu-baseline --no-parity --no-kernel-timing
     KT_FRAMES=4 bash scripts/gpu.sh kt $tag/kt_one_stream --slots 1 --no-cpu-baseline --no-parity --no-roofline-leg --no-kernel-timing ;;
 *)
     echo "usage: scripts/gpu.sh tests|smoke|bench|kt|pmc|sq|evidence <tag> [args]"; exit 2 ;;

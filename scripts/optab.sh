@@ -14,7 +14,7 @@ for rep in $(seq 1 $reps); do
         i=$((i + 1))
         a=$v; [ "$a" = "-" ] && a=""
         echo "== v$i rep $rep :: $a" >> $OUT/ab.log
-        timeout -k 10 300 python -u bench.py --no-cpu-baseline --parity-pixels 64 --steps 3 $a >> $OUT/ab.log 2>&1
+        timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --parity-pixels 64 --steps 3 $a >> $OUT/ab.log 2>&1
     done
 done
 python3 scripts/ab_summary.py $OUT/ab.log > $OUT/ab_summary.txt

@@ -7,6 +7,6 @@ T=gpurun_out/$1
 mkdir -p $T
 timeout -k 10 900 python -u -m pytest tests -x -v -m gpu --timeout 300 --timeout-method thread > $T/pytest_gpu.log 2>&1
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $T/smoke.log 2>&1
-timeout -k 10 400 python -u bench.py > $T/bench.json 2> $T/bench.err
-timeout -k 10 400 python -u bench.py --gpus 2 --dist-backend gloo --config c2 --steps 2 --no-cpu-baseline \
+timeout -k 10 400 python -u bench.py --full > $T/bench.json 2> $T/bench.err
+timeout -k 10 400 python -u bench.py --full --gpus 2 --dist-backend gloo --config c2 --steps 2 --no-cpu-baseline \
     > $T/bench_gloo2.json 2> $T/bench_gloo2.err

@@ -11,7 +11,7 @@ for rep in $(seq 1 $reps); do
         args=""
         for kv in $o; do args="$args --option $kv"; done
         echo "== $o rep $rep" >> $OUT/sweep.log
-        timeout -k 10 300 python -u bench.py --no-cpu-baseline --parity-pixels 64 --steps 3 $args >> $OUT/sweep.log 2>&1
+        timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --parity-pixels 64 --steps 3 $args >> $OUT/sweep.log 2>&1
     done
 done
 python3 - "$OUT/sweep.log" > $OUT/sweep_summary.txt <<'PY'

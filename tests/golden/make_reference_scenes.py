@@ -1,16 +1,16 @@
 """Writes tests/golden/reference_scenes.json: what Scene::from_json
 (src/world/mod.rs:46-49, src/world/json_models.rs:23-48) makes of each file of
-the reference's own scene set (/root/reference/scenes/*.json), through the
+the reference's own scene set (tests/golden/reference_scenes/*.json), through the
 product loader (pt.Scene.from_json, random spheres on, seed 1).
 
 Per file: its sha256, the outcome (ok, or the error the loader reports), the
 shape / material counts and a digest of every realized shape (type, material,
 flags, both 4x4 matrices, parameters) and material (float.hex).  The scene
-files themselves are not copied.  tests/test_reference_scenes.py checks the
-loader and the oracle against the files when the checkout is present, and the
-re-authored scenes/ against the digests when it is not.
+files are kept beside the record as test data (JSON the reference reads, not
+program text).  tests/test_reference_scenes.py checks the loader and the oracle
+against the files, and the re-authored scenes/ against the digests.
 
-    python tests/golden/make_reference_scenes.py [/root/reference/scenes]
+    python tests/golden/make_reference_scenes.py [SCENES_DIR]
 """
 import hashlib
 import json
@@ -50,7 +50,7 @@ def outcome(pt, text, images=None):
 
 
 def main():
-    src = Path(sys.argv[1] if len(sys.argv) > 1 else "/root/reference/scenes")
+    src = Path(sys.argv[1]) if len(sys.argv) > 1 else Path(__file__).resolve().parent / "reference_scenes"
     import __graft_entry__ as ge
     pt = ge.load_package()
     out = {"seed": SEED, "random_spheres": True, "stand_in_image": list(STAND_IN_IMAGE[:2]), "scenes": {}}

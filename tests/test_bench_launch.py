@@ -107,3 +107,34 @@ def test_bench_line_is_strict_json():
                                 "kernels": [1.5, float("-inf")]})
     text = json.dumps(rec, allow_nan=False)
     assert json.loads(text) == {"roofline": {"achieved": None, "frac": None}, "value": 2042.8, "kernels": [1.5, None]}
+
+
+def test_dump_outputs_whole_frame_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a frame within the cap is written whole as float64; a larger one as the same seeded sample
+    of pixels in every run, with the pixel indices beside it, the files together within the cap."""
+    import numpy as np
+    img = np.random.default_rng(7).random((37 * 21, 3))
+    info = bench.dump_outputs(tmp_path / "a", img)
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, img) and info == {"frame": [37 * 21, 3]}
+    assert not (tmp_path / "a" / "frame_pixels.npy").exists()
+    assert 1920 * 1080 * 3 * 8 <= bench.DUMP_CAP_BYTES <= 64 * 10 ** 6  # C2's frame goes out whole
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 3200)  # 100 sampled pixels of the 777
+    for d in ("b", "c"):
+        info = bench.dump_outputs(tmp_path / d, img)
+    assert info == {"frame": [100, 3], "frame_pixels": [100], "of_pixels": 777}
+    px = np.load(tmp_path / "b" / "frame_pixels.npy")
+    assert px.dtype == np.float64 and len(np.unique(px)) == 100 and np.all(np.diff(px) > 0)
+    assert np.array_equal(px, np.load(tmp_path / "c" / "frame_pixels.npy"))
+    sample = np.load(tmp_path / "b" / "frame.npy")
+    assert np.array_equal(sample, img[px.astype(np.int64)])
+    assert sample.nbytes + px.nbytes <= 3200
+
+
+def test_full_is_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 2, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"

@@ -31,7 +31,7 @@ def test_ranks_gather_unshard_parity(world):
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            str(ROOT / "bench.py"), "--gpus", str(world), "--dist-backend", "gloo",
            "--scene", "cornell_box.json", "--width", "320", "--height", "180", "--spp", "4",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]  # --full: the parity section
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="4")
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-4000:]

@@ -3,16 +3,16 @@
 The drop-in claim is that the host loads the reference's scenes/*.json as
 today (Scene::from_json, src/world/mod.rs:46-49; SceneJson,
 src/world/json_models.rs:23-48).  tests/golden/reference_scenes.json records,
-for every file of /root/reference/scenes (made by
+for every file of the reference's scenes/ (kept as test data in
+tests/golden/reference_scenes/; the record is made by
 tests/golden/make_reference_scenes.py), the outcome of pt.Scene.from_json and
 a digest of the realized shapes with their materials:
 
-* with the checkout present (the build container), each file must load (or be
-  refused) exactly as recorded, and the oracle must realize the same shapes and
-  materials bit for bit;
+* each file must load (or be refused) exactly as recorded, and the oracle must
+  realize the same shapes and materials bit for bit;
 * the two scenes the benchmarks use were re-authored in scenes/ (not copied):
   they must realize exactly what the reference's files realize, which is
-  checked against the recorded digests with or without the checkout.
+  checked against the recorded digests.
 
 Outcomes that match the reference's: dupin.json is in an older schema (no
 `camera`, no `materials` map) and serde fails on it too; detached_materials.json
@@ -33,17 +33,15 @@ HERE = Path(__file__).resolve().parent
 sys.path.insert(0, str(HERE / "golden"))
 import make_reference_scenes as M  # noqa: E402
 
-REF_SCENES = Path("/root/reference/scenes")
+REF_SCENES = HERE / "golden" / "reference_scenes"
 FIXTURE = json.loads((HERE / "golden" / "reference_scenes.json").read_text())
 NAMES = sorted(FIXTURE["scenes"])
-checkout = pytest.mark.skipif(not REF_SCENES.is_dir(), reason="reference checkout not present")
 
 
 def _images(rec):
     return {n: M.STAND_IN_IMAGE for n in rec["with_loader"]["images"]}
 
 
-@checkout
 def test_fixture_covers_the_reference_scene_set():
     files = sorted(f.name for f in REF_SCENES.glob("*.json"))
     assert files == NAMES
@@ -51,7 +49,6 @@ def test_fixture_covers_the_reference_scene_set():
         assert hashlib.sha256((REF_SCENES / n).read_bytes()).hexdigest() == FIXTURE["scenes"][n]["sha256"], n
 
 
-@checkout
 @pytest.mark.parametrize("name", NAMES)
 def test_reference_scene_loads_as_recorded(pt, name):
     rec = FIXTURE["scenes"][name]
@@ -71,7 +68,6 @@ def test_reference_scene_loads_as_recorded(pt, name):
                (wl["outcome"], wl["shapes"], wl["materials"], wl["digest"])
 
 
-@checkout
 @pytest.mark.parametrize("name", [n for n in NAMES if FIXTURE["scenes"][n]["outcome"] == "ok"
                                   or "with_loader" in FIXTURE["scenes"][n]])
 def test_reference_scene_realized_bit_equal_to_oracle(pt, name):
