@@ -26,8 +26,6 @@ struct DeviceScene {
     unsigned long long *guard = nullptr;  // device counter of marches dropped by the march guard
 };
 
-// Device workspace of the wavefront engine (pt_wave.hip), grown on demand and
-// reused by every frame of a renderer.
 // Per-kernel launch timing (pt_kernel_timing): HIP events recorded on the
 // launch stream around every render-path kernel while enabled.
 // (kind 5 was the wavefront tail kernel until round 6; it now times the per-slot unwind, wf_unwind)
@@ -72,6 +70,8 @@ extern const char *const TUNING_NAMES[];  // null-terminated
 #define PT_WAVE_DIAG 0
 #endif
 
+// Device workspace of the wavefront engine (pt_wave.hip), grown on demand and
+// reused by every frame of a renderer.
 struct WaveWorkspace {
     Tuning tune;  // this renderer's knobs (both engines read them from here)
     void *base = nullptr;

@@ -5,6 +5,8 @@
 #pragma once
 #include <cstdint>
 
+#include "pt_dims.hpp"  // TILE
+
 namespace pt {
 
 enum ShapeKind : int32_t { SPHERE = 0, RECTANGLE = 1, CUBE = 2, MARCH = 3, TORUS = 4 };
@@ -154,7 +156,6 @@ struct Ctr {
     uint64_t c[C_COUNT];
 };
 
-constexpr uint32_t TILE = 16;  // 16x16 pixels = one 256-thread workgroup
 constexpr double T_MIN = 0.001;  // ray_color: closest_hit(ray, 0.001, INF), src/renderer/mod.rs:24
 
 }  // namespace pt

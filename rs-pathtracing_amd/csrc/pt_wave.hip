@@ -45,6 +45,7 @@
 
 #include "pt_device.hpp"
 #include "pt_kernel.hpp"
+#include "pt_plan.hpp"
 
 namespace pt {
 
@@ -78,7 +79,7 @@ __host__ __device__ __forceinline__ int unpack_who(uint32_t w) { return (int)(w 
 struct PathSoA {
     char *base;
     size_t cap;  // a multiple of 64
-    static constexpr size_t BYTES = 8 * 8 + 2 * 4;  // per path
+    static constexpr size_t BYTES = PATH_BYTES;  // per path: eight 8-byte fields and two 4-byte ones
     static constexpr uint32_t BLK = 64, BLK_BYTES = (uint32_t)BYTES * BLK;
     enum F8 : int { OX, OY, OZ, DX, DY, DZ, T, RNG };
     enum F4 : int { WHO, SID };
@@ -476,8 +477,7 @@ __global__ __launch_bounds__(256, WAVES) void wf_bounce(const WfArgs *__restrict
 // march waves coherent.  March jobs the bounce kernel predicts long (bit 2:
 // the ray passes close to the marched shape's centre) go first in the queue,
 // each class in id order, so the persistent march grid's tail is made of
-// short jobs.
-constexpr int CP_ITEMS = 16, CP_BLOCK = 256, CP_TILE = CP_ITEMS * CP_BLOCK;
+// short jobs.  (CP_ITEMS statuses per thread, CP_BLOCK threads, CP_TILE statuses per tile: pt_dims.hpp)
 
 __device__ __forceinline__ void cp_bits(uint4 q, uint32_t *live, uint32_t *march, uint32_t *lng) {
     // statuses are 0, 1, 3 or 7: bit 0 of each byte = live, bit 1 = march, bit 2 = predicted long
@@ -1134,31 +1134,7 @@ hipError_t timer_collect(KernelTimer *t, double *ms, uint32_t *launches) {
 }
 
 // ------------------------------------------------------------- host driver
-static void free_args(WaveWorkspace *ws);
-void wave_workspace_free(WaveWorkspace *ws) {
-    for (int k = 0; k < WaveWorkspace::MAX_SLOTS - 1; k++) {
-        if (ws->side[k]) (void)hipStreamDestroy(ws->side[k]);
-        if (ws->join[k]) (void)hipEventDestroy(ws->join[k]);
-        ws->side[k] = nullptr;
-        ws->join[k] = nullptr;
-    }
-    free_args(ws);
-    if (ws->fork) (void)hipEventDestroy(ws->fork);
-    if (ws->reduced) (void)hipEventDestroy(ws->reduced);
-    if (ws->done) (void)hipEventDestroy(ws->done);
-    if (ws->args_ev) (void)hipEventDestroy(ws->args_ev);
-    ws->fork = ws->reduced = ws->done = ws->args_ev = nullptr;
-    ws->used = false;
-    timer_free(ws->timer);
-    ws->timer = nullptr;
-    if (ws->diag) (void)hipFree(ws->diag);
-    ws->diag = nullptr;
-    if (ws->base) (void)hipFree(ws->base);
-    ws->base = nullptr;
-    ws->bytes = 0;
-}
-
-// The launches' argument blocks: a pinned host staging buffer and its device copy (render_wave).
+// The launches' argument blocks: a pinned host staging buffer and its device copy (launch_render_wave).
 static void free_args(WaveWorkspace *ws) {
     if (ws->args_pending && ws->args_ev) (void)hipEventSynchronize(ws->args_ev);
     if (ws->args_host) (void)hipHostFree(ws->args_host);
@@ -1166,6 +1142,35 @@ static void free_args(WaveWorkspace *ws) {
     ws->args_host = ws->args_dev = nullptr;
     ws->args_bytes = 0;
     ws->args_pending = false;
+}
+
+// The workspace's streams and events, and with them the argument blocks whose copy args_ev marks: all belong to
+// one device.
+static void release_streams(WaveWorkspace *ws) {
+    free_args(ws);
+    for (int k = 0; k < WaveWorkspace::MAX_SLOTS - 1; k++) {
+        if (ws->side[k]) (void)hipStreamDestroy(ws->side[k]);
+        if (ws->join[k]) (void)hipEventDestroy(ws->join[k]);
+        ws->side[k] = nullptr;
+        ws->join[k] = nullptr;
+    }
+    if (ws->fork) (void)hipEventDestroy(ws->fork);
+    if (ws->reduced) (void)hipEventDestroy(ws->reduced);
+    if (ws->done) (void)hipEventDestroy(ws->done);
+    if (ws->args_ev) (void)hipEventDestroy(ws->args_ev);
+    ws->fork = ws->reduced = ws->done = ws->args_ev = nullptr;
+    ws->used = false;
+}
+
+void wave_workspace_free(WaveWorkspace *ws) {
+    release_streams(ws);
+    timer_free(ws->timer);
+    ws->timer = nullptr;
+    if (ws->diag) (void)hipFree(ws->diag);
+    ws->diag = nullptr;
+    if (ws->base) (void)hipFree(ws->base);
+    ws->base = nullptr;
+    ws->bytes = 0;
 }
 
 static hipError_t reserve_args(WaveWorkspace *ws, size_t bytes) {
@@ -1213,15 +1218,32 @@ static hipError_t reserve(WaveWorkspace *ws, size_t bytes) {
     return hipSuccess;
 }
 
-// BVH nodes per octant layout from which the bounce runs its FMA_SLAB build
-// (dev::closest_nomarch): C5's 100k-sphere tree has ~200k, cornell's ~960.
-// The scenes whose BVH walk runs in wf_walk (Tuning::wf_walk): a large tree and no marched shape (C5).
+// Exactly the resident blocks of one kernel build (persistent grids).
+template <class K>
+static uint32_t resident_blocks(K kern) {
+    int dev = 0, cus = 256, occ = 0;
+    if (hipGetDevice(&dev) == hipSuccess) {
+        hipDeviceProp_t pr;
+        if (hipGetDeviceProperties(&pr, dev) == hipSuccess) cus = pr.multiProcessorCount;
+    }
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 256, 0) != hipSuccess || occ < 1) occ = 1;
+    return (uint32_t)(cus * occ);
+}
+
+// The persistent march grid: exactly the resident blocks of the device (a half-machine grid measured slower).
+static uint32_t march_grid() {
+    static const uint32_t blocks = resident_blocks(wf_march<march::F_HEART>);
+    return blocks;
+}
+
+// The scenes whose BVH walk runs in wf_walk (Tuning::wf_walk): a large tree (BIG_BVH_NODES, pt_types.hpp: C5's
+// 100k-sphere tree has ~200k nodes, cornell's ~960) and no marched shape.
 static bool walk_split(const dev::Scene &sc, const Tuning &tu) {
     return tu.wf_walk && !sc.ext && sc.nnodes >= BIG_BVH_NODES && sc.nmarch == 0;
 }
 
 template <bool FIRST>
-static void launch_bounce(uint32_t blocks, hipStream_t st, const dev::Scene &sc, const WfArgs *A, int it,
+static void launch_bounce_build(uint32_t blocks, hipStream_t st, const dev::Scene &sc, const WfArgs *A, int it,
                           unsigned long long *diag, int fkind, int waves, bool split) {
     if (split) {  // shade and store the new ray only: wf_walk traces it
         switch (waves) {
@@ -1265,16 +1287,70 @@ static void launch_bounce(uint32_t blocks, hipStream_t st, const dev::Scene &sc,
     }
 }
 
-// Exactly the resident blocks of one kernel build (persistent grids).
-template <class K>
-static uint32_t resident_blocks(K kern) {
-    int dev = 0, cus = 256, occ = 0;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        hipDeviceProp_t pr;
-        if (hipGetDeviceProperties(&pr, dev) == hipSuccess) cus = pr.multiProcessorCount;
+// The bounce of iteration it: the chunk's camera rays (first), or the live list of it.
+static void launch_bounce(bool first, uint32_t blocks, hipStream_t st, const dev::Scene &sc, const WfArgs *A, int it,
+                          unsigned long long *diag, int fkind, int waves, bool split) {
+    if (first)
+        launch_bounce_build<true>(blocks, st, sc, A, it, diag, fkind, waves, split);
+    else
+        launch_bounce_build<false>(blocks, st, sc, A, it, diag, fkind, waves, split);
+}
+
+// The new rays' BVH walk, over the live list of it + 1 (walk_split scenes).
+static void launch_walk(uint32_t blocks, hipStream_t st, const dev::Scene &sc, const WfArgs *A, int it, int waves) {
+    if (!sc.qnodes) {  // (a tree without the quantized form)
+        wf_walk<5, false><<<blocks, 256, 0, st>>>(A, it);
+        return;
     }
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 256, 0) != hipSuccess || occ < 1) occ = 1;
-    return (uint32_t)(cus * occ);
+    switch (waves) {  // the walk's register budget, waves per SIMD (Tuning::wf_walk)
+    case 4: wf_walk<4, true><<<blocks, 256, 0, st>>>(A, it); break;
+    case 6: wf_walk<6, true><<<blocks, 256, 0, st>>>(A, it); break;
+    case 8: wf_walk<8, true><<<blocks, 256, 0, st>>>(A, it); break;
+    default: wf_walk<5, true><<<blocks, 256, 0, st>>>(A, it); break;
+    }
+}
+
+// The march queue of iteration it, on the persistent grid.
+static void launch_march(hipStream_t st, const WfArgs *A, int it, unsigned long long *diag, int fkind,
+                         uint32_t slice) {
+    const uint32_t blocks = march_grid();
+    if (fkind != march::F_HEART)  // another ray-marched function: the generic build
+        wf_march<march::F_ANY><<<blocks, 256, 0, st>>>(A, it, nullptr, slice);
+    else
+        wf_march<march::F_HEART><<<blocks, 256, 0, st>>>(A, it, diag, slice);
+}
+
+// One thread per slot of a chunk of few pixels (UNWIND_PIXELS).
+static void launch_unwind(uint32_t slots, hipStream_t st, const dev::Scene &sc, const WfArgs *A) {
+    if (sc.ext)
+        wf_unwind<true><<<(slots + 255) / 256, 256, 0, st>>>(A);
+    else
+        wf_unwind<false><<<(slots + 255) / 256, 256, 0, st>>>(A);
+}
+
+// One thread per pixel; unwound: wf_unwind has run over the chunk's slots.
+static void launch_reduce(uint32_t npix, hipStream_t st, const dev::Scene &sc, const WfArgs *A, bool unwound,
+                          int first, int last, double *out) {
+    const uint32_t blocks = (npix + 255) / 256;
+    if (sc.ext && unwound)
+        wf_reduce<true, true><<<blocks, 256, 0, st>>>(A, first, last, out);
+    else if (sc.ext)
+        wf_reduce<true, false><<<blocks, 256, 0, st>>>(A, first, last, out);
+    else if (unwound)
+        wf_reduce<false, true><<<blocks, 256, 0, st>>>(A, first, last, out);
+    else
+        wf_reduce<false, false><<<blocks, 256, 0, st>>>(A, first, last, out);
+}
+
+// One timed launch (or group of launches under one record) on a chunk's stream: the timer's events around it when
+// kernel timing is on (pt_kernel_timing), and the launch's error.
+template <class F>
+static hipError_t timed(KernelTimer *t, hipStream_t st, int kind, F launch) {
+    hipError_t e = timer_begin(t, st, kind);
+    if (e != hipSuccess) return e;
+    launch();
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    return timer_end(t, st);
 }
 
 // Chunks in flight (Tuning::wf_slots): each has its own path state (slot) and
@@ -1288,20 +1364,7 @@ static hipError_t ensure_streams(WaveWorkspace *ws, int slots) {
     if (ws->device != dev) {  // streams and events belong to one device
         // the previous frame must be done with the streams and the workspace
         if (ws->used && ws->done && (e = hipEventSynchronize(ws->done)) != hipSuccess) return e;
-        free_args(ws);  // (the device blocks live on the old device)
-        if (ws->args_ev) (void)hipEventDestroy(ws->args_ev);
-        ws->args_ev = nullptr;
-        for (int k = 0; k < WaveWorkspace::MAX_SLOTS - 1; k++) {
-            if (ws->side[k]) (void)hipStreamDestroy(ws->side[k]);
-            if (ws->join[k]) (void)hipEventDestroy(ws->join[k]);
-            ws->side[k] = nullptr;
-            ws->join[k] = nullptr;
-        }
-        if (ws->fork) (void)hipEventDestroy(ws->fork);
-        if (ws->reduced) (void)hipEventDestroy(ws->reduced);
-        if (ws->done) (void)hipEventDestroy(ws->done);
-        ws->fork = ws->reduced = ws->done = nullptr;
-        ws->used = false;
+        release_streams(ws);  // (the argument blocks live on the old device too)
         ws->device = dev;
     }
     if (!ws->fork && (e = hipEventCreateWithFlags(&ws->fork, hipEventDisableTiming)) != hipSuccess) return e;
@@ -1315,166 +1378,77 @@ static hipError_t ensure_streams(WaveWorkspace *ws, int slots) {
     return hipSuccess;
 }
 
-// Chunks keep at least MIN_CHUNK_PATHS paths to fill the device (Tuning::wf_min_chunks).
-constexpr uint32_t MIN_CHUNK_PATHS = 1u << 21;
-
+// One slot of the workspace (plan::Layout): the path state of a chunk in flight.
 struct Slot {
     WfView v;
     uint32_t *cp_blk;
     PathSoA set[2];  // iteration it reads set[it & 1] and writes set[(it + 1) & 1]
 };
 
-static hipError_t render_wave(const dev::Scene &sc, const FrameParams &P0, double *out, hipStream_t st,
-                                 WaveWorkspace *ws, int fkind) {
+// Slot j's stream: the caller's, then the side streams.
+static hipStream_t slot_stream(const WaveWorkspace *ws, hipStream_t st, int j) { return j == 0 ? st : ws->side[j - 1]; }
+
+// Queues this rank's tiles of the frame (of a resumable frame: the window [s_begin, s_end) of its samples) on st:
+// the plan (pt_plan.hpp), the workspace, the chunks' argument blocks, then the chunks step by step.
+hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, double *out, hipStream_t st,
+                              WaveWorkspace *ws, int fkind) {
+    if (P0.tile_count == 0 || P0.spp == 0) return hipSuccess;
     const Tuning &tu = ws->tune;
-    // the launch's samples: the frame's, or a resumable frame's window [s_begin, s_end) of them
-    const uint32_t s_begin = P0.s_begin, s_end = P0.s_end ? P0.s_end : P0.spp, nsw = s_end - s_begin;
-    const uint32_t ntiles = P0.tile_count;
-    const int iters = (int)P0.depth + 2;  // traces per path <= depth + 1, then one last shade
-    const size_t cnt_words = (size_t)(iters + 2) * 4;
-    auto al = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    plan::Input in;
+    in.ntiles = P0.tile_count;
+    in.s_begin = P0.s_begin;
+    in.s_end = P0.s_end ? P0.s_end : P0.spp;
+    in.spp = P0.spp;
+    in.depth = P0.depth;
+    in.progressive = P0.stop != nullptr;
+    in.textured = sc.tex != nullptr;
     // pre-selected march jobs (one marched shape): the bounce kernel hands the march its object-space ray
     // and bound (C2 +9 %: iso march 340 -> 275 ms, bounce 248 -> 256, round 1)
-    const bool presel = sc.nmarch == 1 && !ws->diag;
-    // The chunk plan for cap_want path slots per chunk: tile groups (only for frames beyond cap_want pixels),
-    // then sample chunks, the streams, and the workspace bytes.
-    struct Plan {
-        uint32_t group_tiles, npix_max, ns, cap, cap_tiles;
-        int slots;
-        size_t att_bytes, slot_bytes, bytes;
-    };
-    auto plan_for = [&](uint32_t cap_want) {
-        Plan pl;
-        const uint32_t tiles_per_group = cap_want / (TILE * TILE) ? cap_want / (TILE * TILE) : 1;
-        pl.group_tiles = ntiles < tiles_per_group ? ntiles : tiles_per_group;
-        pl.npix_max = pl.group_tiles * TILE * TILE;
-        uint32_t ns = cap_want / pl.npix_max;
-        if (ns < 1) ns = 1;
-        if (ns > nsw) ns = nsw;
-        // A small frame (one rank's share of a multi-GPU frame) still gets at least wf_min_chunks sample
-        // chunks, so the pipelined slots overlap one chunk's short tail iterations with the next chunk's work;
-        // chunks keep at least MIN_CHUNK_PATHS paths to fill the device.  (A progressive frame's band, P0.stop
-        // set, gets at least two: one per chunk stream; and any frame at least one per chunk stream while its
-        // chunks keep MIN_CHUNK_PATHS paths, whatever wf_paths allows.)
-        uint32_t mc = P0.stop && tu.wf_min_chunks < 2 ? 2u : (uint32_t)tu.wf_min_chunks;
-        if (mc < (uint32_t)tu.wf_slots) mc = (uint32_t)tu.wf_slots;
-        if (mc > 1 && ntiles <= pl.group_tiles) {
-            uint32_t want = (nsw + mc - 1) / mc;
-            const uint32_t floor_ns = (MIN_CHUNK_PATHS + pl.npix_max - 1) / pl.npix_max;
-            if (want < floor_ns) want = floor_ns;
-            if (want < ns) ns = want;
-        }
-        pl.ns = ns;
-        pl.cap = ns * pl.npix_max;
-        pl.cap_tiles = (pl.cap + CP_TILE - 1) / CP_TILE;  // compaction tiles (status padded to them)
-        // no more slots than chunks
-        const uint64_t chunks = (uint64_t)((ntiles + pl.group_tiles - 1) / pl.group_tiles) * ((nsw + ns - 1) / ns);
-        pl.slots = tu.wf_slots;
-        if ((uint64_t)pl.slots > chunks) pl.slots = (int)chunks;
-        const size_t cap = pl.cap;
-        pl.att_bytes = sc.tex ? cap * 24 * (P0.depth + 1) : 0;  // textured attenuation values
-        // two path-state sets, leaf records, lists, id stacks, statuses, compaction tiles, counters
-        pl.slot_bytes = al(cap * PathSoA::BYTES) * 2 + al(cap * 32) + (presel ? al(cap * 64) : 0) + al(cap * 4) * 2 +
-                        al(cap * 4 * (P0.depth + 1)) + al((size_t)pl.cap_tiles * CP_TILE) +
-                        al(((size_t)pl.cap_tiles + CP_BLOCK) * 12) + al(cnt_words * 4) + al(pl.att_bytes);
-        pl.bytes = pl.slot_bytes * (size_t)pl.slots + al((size_t)pl.npix_max * 24) + 8192;
-        return pl;
-    };
-    // Path slots per chunk: Tuning::wf_paths, or by depth (deep frames: bigger chunks, fewer tails), halved
-    // until the plan fits the device memory the workspace may take (what is free plus what it holds now, less
-    // 2 GiB): a deep textured frame's per-slot attenuation values ((depth + 1) * 24 B per path) would otherwise
-    // ask for more than the device has (1080p, 256 spp, depth 50 at 128M paths needed ~430 GB).
-    // (deep frames: 256M paths, two chunks of a 1080p x 256-spp frame in one step, ~120 GB per chunk stream at depth
-    // 50: one tail of late iterations instead of two, C2 depth 50 1237 -> 1251, profiles/r6/ab/r6aa_*; 128M until round 6)
-    uint32_t cap_want = tu.wf_paths ? (uint32_t)tu.wf_paths : (P0.depth > 16 ? 1u << 28 : 3u << 24);
-    Plan pl = plan_for(cap_want);
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const size_t reserve_b = (size_t)2 << 30;
-            const size_t avail = free_b + ws->bytes > reserve_b ? free_b + ws->bytes - reserve_b : 0;
-            while (pl.bytes > avail && cap_want > MIN_CHUNK_PATHS) {
-                cap_want = cap_want / 2 > MIN_CHUNK_PATHS ? cap_want / 2 : MIN_CHUNK_PATHS;
-                pl = plan_for(cap_want);
-            }
-        }
-    }
-    const uint32_t group_tiles = pl.group_tiles, npix_max = pl.npix_max, ns = pl.ns, cap = pl.cap,
-                   cap_tiles = pl.cap_tiles;
-    const int slots = pl.slots;
-    const size_t att_bytes = pl.att_bytes, bytes = pl.bytes;
+    in.presel = sc.nmarch == 1 && !ws->diag;
+    in.wf_paths = tu.wf_paths;
+    in.wf_slots = tu.wf_slots;
+    in.wf_min_chunks = tu.wf_min_chunks;
+    // the workspace may take what is free plus what it holds now, less the reserve
+    in.avail_bytes = plan::MEM_UNKNOWN;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+        in.avail_bytes = free_b + ws->bytes > plan::RESERVE_BYTES ? free_b + ws->bytes - plan::RESERVE_BYTES : 0;
+    const plan::Plan pl = plan::make_plan(in);
+    const plan::Layout &L = pl.lay;
+    const std::vector<plan::Chunk> chunk_list = plan::chunk_list(in, pl);
+    const int slots = pl.slots, iters = pl.iters;
+    const uint32_t s_begin = in.s_begin, s_end = in.s_end;
+
     hipError_t e = ensure_streams(ws, slots);
     if (e != hipSuccess) return e;
     // One workspace serves every frame of the renderer, whichever stream it is
     // queued on (render_start's own stream, a caller's stream in
     // render_device): this frame's kernels wait for the previous frame's.
     if (ws->used && (e = hipStreamWaitEvent(st, ws->done, 0)) != hipSuccess) return e;
-    e = reserve(ws, bytes);
-    if (e != hipSuccess) return e;
-    // carve the workspace: the slots' path state, then the shared running sums
-    char *p = (char *)ws->base;
-    auto take = [&](size_t n) {
-        char *r = p;
-        p += al(n);
-        return (void *)r;
-    };
+    if ((e = reserve(ws, pl.bytes)) != hipSuccess) return e;
+    // the slots' path state and the running sums they share, where the layout puts them
     Slot sl[WaveWorkspace::MAX_SLOTS];
     for (int k = 0; k < slots; k++) {
+        char *slot = (char *)ws->base + (size_t)k * L.slot_stride;
+        auto at = [&](plan::Region r) { return L.size[r] ? (void *)(slot + L.off[r]) : nullptr; };
+        sl[k].set[0] = PathSoA{(char *)at(plan::R_SET0), pl.cap};
+        sl[k].set[1] = PathSoA{(char *)at(plan::R_SET1), pl.cap};
+        sl[k].cp_blk = (uint32_t *)at(plan::R_CP_BLK);
         WfView &v = sl[k].v;
-        for (int h = 0; h < 2; h++) {
-            PathSoA &S = sl[k].set[h];
-            S.base = (char *)take((size_t)cap * PathSoA::BYTES);
-            S.cap = cap;
-        }
-        v.ids = (uint32_t *)take((size_t)cap * 4 * (P0.depth + 1));
-        v.leaf = (double *)take((size_t)cap * 32);  // 32-byte leaf records (end_path)
-        v.list = (uint32_t *)take((size_t)cap * 4);
-        v.mq = (uint32_t *)take((size_t)cap * 4);
-        v.status = (uint8_t *)take((size_t)cap_tiles * CP_TILE);
-        sl[k].cp_blk = (uint32_t *)take(((size_t)cap_tiles + CP_BLOCK) * 12);  // CpLayout: 3 x per * 256 words
-        v.cnt = (uint32_t *)take(cnt_words * 4);
-        v.att = att_bytes ? (double *)take(att_bytes) : nullptr;
-        v.jo = presel ? (double2 *)take((size_t)cap * 64) : nullptr;
-        v.cap = cap;
+        v.ids = (uint32_t *)at(plan::R_IDS);
+        v.leaf = (double *)at(plan::R_LEAF);
+        v.list = (uint32_t *)at(plan::R_LIST);
+        v.mq = (uint32_t *)at(plan::R_MQ);
+        v.status = (uint8_t *)at(plan::R_STATUS);
+        v.cnt = (uint32_t *)at(plan::R_CNT);
+        v.att = (double *)at(plan::R_ATT);
+        v.jo = (double2 *)at(plan::R_JO);
+        v.acc = (double *)((char *)ws->base + L.acc);
+        v.cap = pl.cap;
     }
-    double *acc = (double *)take((size_t)npix_max * 24);
-    for (int k = 0; k < slots; k++) sl[k].v.acc = acc;
-    if ((size_t)(p - (char *)ws->base) > ws->bytes) return hipErrorOutOfMemory;
 
-    // persistent march grid: exactly the resident blocks of the device (a half-machine grid measured slower)
-    static const uint32_t march_blocks = resident_blocks(wf_march<march::F_HEART>);
     const uint32_t march_slice = (uint32_t)tu.wf_march_slice;
     const bool split = walk_split(sc, tu);
-    // Chunk j of step k runs on stream j (its path-state slot); a step's chunks
-    // are enqueued iteration by iteration across the step.  (Measured slower and
-    // removed in round 6, DESIGN.md §5: bounce or march launches chained across
-    // the streams, side streams at another priority, streams staggered by part
-    // of a chunk, a tail kernel running a chunk's last paths to their ends.)
-    struct Chunk {
-        uint32_t g0, gt, s0, ns;
-        int slot;
-        uint32_t step;
-    };
-    // Sample chunks of a tile group: as few as fit ns samples each, rounded up
-    // to whole rounds of `slots` (no round with an idle stream), with the
-    // samples spread evenly over them (no short last chunk).  The per-pixel
-    // sums take the chunks in sample order either way.
-    uint32_t nchunks = (nsw + ns - 1) / ns;
-    if (slots > 1 && nchunks > 1 && nchunks % (uint32_t)slots) nchunks += (uint32_t)slots - nchunks % (uint32_t)slots;
-    if (nchunks > nsw) nchunks = nsw;
-    const uint32_t S = (uint32_t)slots;
-    std::vector<Chunk> chunk_list;
-    uint32_t step0 = 0;
-    for (uint32_t g0 = 0; g0 < ntiles; g0 += group_tiles) {
-        const uint32_t gt = ntiles - g0 < group_tiles ? ntiles - g0 : group_tiles;
-        uint32_t s0 = s_begin;
-        for (uint32_t c = 0; c < nchunks; c++) {
-            const uint32_t s1 = s_begin + (uint32_t)((uint64_t)nsw * (c + 1) / nchunks);  // <= ceil(nsw / nchunks) <= ns
-            chunk_list.push_back(Chunk{g0, gt, s0, s1 - s0, (int)(c % S), step0 + c / S});
-            s0 = s1;
-        }
-        step0 += (nchunks + S - 1) / S;
-    }
     // The launches' argument blocks (WfArgs): chunk ci at iteration parity h is block 2 ci + h.  They are
     // written to the pinned staging buffer, which the previous frame's copy must have read, and copied to the
     // device on st after the previous frame's kernels (the wait on ws->done above), before the side streams fork.
@@ -1482,7 +1456,7 @@ static hipError_t render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
     if ((e = reserve_args(ws, nargs * sizeof(WfArgs))) != hipSuccess) return e;
     WfArgs *ah = (WfArgs *)ws->args_host, *ad = (WfArgs *)ws->args_dev;
     for (size_t ci = 0; ci < chunk_list.size(); ci++) {
-        const Chunk &ch = chunk_list[ci];
+        const plan::Chunk &ch = chunk_list[ci];
         const int j = ch.slot;
         WfView v = sl[j].v;
         v.tile0 = P0.tile_begin + ch.g0;
@@ -1504,13 +1478,18 @@ static hipError_t render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
         for (int k = 0; k < slots - 1; k++)
             if ((e = hipStreamWaitEvent(ws->side[k], ws->fork, 0)) != hipSuccess) return e;
     }
+    // Chunk j of step k runs on stream j (its path-state slot); a step's chunks
+    // are enqueued iteration by iteration across the step.  (Measured slower and
+    // removed in round 6, DESIGN.md §5: bounce or march launches chained across
+    // the streams, side streams at another priority, streams staggered by part
+    // of a chunk, a tail kernel running a chunk's last paths to their ends.)
     for (size_t r0 = 0; r0 < chunk_list.size();) {
         size_t r1 = r0;  // the step's chunks [r0, r1), in sample order, at most one per stream
         while (r1 < chunk_list.size() && chunk_list[r1].step == chunk_list[r0].step) r1++;
         for (size_t c = r0; c < r1; c++) {  // the step's chunks: cleared counters
             const int j = chunk_list[c].slot;
-            const hipStream_t cs = j == 0 ? st : ws->side[j - 1];
-            if ((e = hipMemsetAsync(sl[j].v.cnt, 0, cnt_words * 4, cs)) != hipSuccess) return e;
+            const hipStream_t cs = slot_stream(ws, st, j);
+            if ((e = hipMemsetAsync(sl[j].v.cnt, 0, pl.cnt_words * 4, cs)) != hipSuccess) return e;
             if (P0.stop) {
                 stop_gate<<<1, 64, 0, cs>>>(P0.stop, sl[j].v.cnt, -1);
                 if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -1518,71 +1497,48 @@ static hipError_t render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
         }
         for (int it = 0; it < iters; it++) {
             for (size_t c = r0; c < r1; c++) {
-                const Chunk &ch = chunk_list[c];
-                const int j = ch.slot;
-                const hipStream_t cs = j == 0 ? st : ws->side[j - 1];
+                const plan::Chunk &ch = chunk_list[c];
+                const hipStream_t cs = slot_stream(ws, st, ch.slot);
                 const WfArgs *A = ad + 2 * c + (it & 1);
-                const WfView &v = sl[j].v;
-                uint32_t *cp_blk = sl[j].cp_blk;
+                const WfView &v = sl[ch.slot].v;
+                uint32_t *cp_blk = sl[ch.slot].cp_blk;
                 const uint32_t paths = ch.ns * ch.gt * TILE * TILE;
                 uint32_t bb = (paths + 255) / 256;
                 if (bb > WF_BOUNCE_CAP) bb = WF_BOUNCE_CAP;
                 // iteration 0: slots [0, paths) are the chunk's camera rays
-                if ((e = timer_begin(ws->timer, cs, K_BOUNCE)) != hipSuccess) return e;
-                if (it == 0)
-                    launch_bounce<true>((paths + 255) / 256, cs, sc, A, 0, ws->diag, fkind, tu.wf_bounce_waves,
-                                            split);
-                else
-                    launch_bounce<false>(bb, cs, sc, A, it, ws->diag, fkind, tu.wf_bounce_waves, split);
-                if ((e = hipGetLastError()) != hipSuccess) return e;
-                if ((e = timer_end(ws->timer, cs)) != hipSuccess) return e;
+                e = timed(ws->timer, cs, K_BOUNCE, [&] {
+                    launch_bounce(it == 0, it == 0 ? (paths + 255) / 256 : bb, cs, sc, A, it, ws->diag, fkind,
+                                  tu.wf_bounce_waves, split);
+                });
+                if (e != hipSuccess) return e;
                 if (it == iters - 1) continue;  // the last bounce only shades
                 // live list for it + 1 and march queue for it, both id-sorted
-                if ((e = timer_begin(ws->timer, cs, K_SELECT)) != hipSuccess) return e;
-                const uint32_t ptiles = (paths + CP_TILE - 1) / CP_TILE;
-                const uint32_t *n_in = it == 0 ? nullptr : &v.cnt[it * 4 + 0];  // the bounce's input count
-                const CpLayout L = CpLayout::of(ptiles);
-                const uint32_t cgrid = CP_GRID && ptiles > CP_GRID ? CP_GRID : ptiles;
-                cp_count<<<cgrid, CP_BLOCK, 0, cs>>>(v.status, cp_blk, L, n_in, paths);
-                cp_scan<<<1, CP_BLOCK, 0, cs>>>(cp_blk, ptiles, L, n_in, paths, &v.cnt[(it + 1) * 4 + 0],
-                                                &v.cnt[it * 4 + 1], &v.cnt[it * 4 + 2]);
-                cp_scatter<<<cgrid, CP_BLOCK, 0, cs>>>(v.status, cp_blk, L, &v.cnt[it * 4 + 2], v.list, v.mq, n_in,
-                                                       paths);
-                if (P0.stop) stop_gate<<<1, 64, 0, cs>>>(P0.stop, v.cnt, it);
-                if ((e = hipGetLastError()) != hipSuccess) return e;
-                if ((e = timer_end(ws->timer, cs)) != hipSuccess) return e;
-                if (split) {  // the new rays' BVH walk, over the live list of it + 1
-                    if ((e = timer_begin(ws->timer, cs, K_WALK)) != hipSuccess) return e;
-                    if (!sc.qnodes) {  // (a tree without the quantized form)
-                        wf_walk<5, false><<<bb, 256, 0, cs>>>(A, it);
-                    } else {
-                        switch (tu.wf_walk) {  // the walk's register budget, waves per SIMD
-                        case 4: wf_walk<4, true><<<bb, 256, 0, cs>>>(A, it); break;
-                        case 6: wf_walk<6, true><<<bb, 256, 0, cs>>>(A, it); break;
-                        case 8: wf_walk<8, true><<<bb, 256, 0, cs>>>(A, it); break;
-                        default: wf_walk<5, true><<<bb, 256, 0, cs>>>(A, it); break;
-                        }
-                    }
-                    if ((e = hipGetLastError()) != hipSuccess) return e;
-                    if ((e = timer_end(ws->timer, cs)) != hipSuccess) return e;
+                e = timed(ws->timer, cs, K_SELECT, [&] {
+                    const uint32_t ptiles = (paths + CP_TILE - 1) / CP_TILE;
+                    const uint32_t *n_in = it == 0 ? nullptr : &v.cnt[it * 4 + 0];  // the bounce's input count
+                    const CpLayout CL = CpLayout::of(ptiles);
+                    const uint32_t cgrid = CP_GRID && ptiles > CP_GRID ? CP_GRID : ptiles;
+                    cp_count<<<cgrid, CP_BLOCK, 0, cs>>>(v.status, cp_blk, CL, n_in, paths);
+                    cp_scan<<<1, CP_BLOCK, 0, cs>>>(cp_blk, ptiles, CL, n_in, paths, &v.cnt[(it + 1) * 4 + 0],
+                                                    &v.cnt[it * 4 + 1], &v.cnt[it * 4 + 2]);
+                    cp_scatter<<<cgrid, CP_BLOCK, 0, cs>>>(v.status, cp_blk, CL, &v.cnt[it * 4 + 2], v.list, v.mq,
+                                                           n_in, paths);
+                    if (P0.stop) stop_gate<<<1, 64, 0, cs>>>(P0.stop, v.cnt, it);
+                });
+                if (e != hipSuccess) return e;
+                if (split) {
+                    e = timed(ws->timer, cs, K_WALK, [&] { launch_walk(bb, cs, sc, A, it, tu.wf_walk); });
+                    if (e != hipSuccess) return e;
                 }
                 if (sc.nmarch == 0) continue;  // no ray-marched shape: the march queue is always empty
-                if ((e = timer_begin(ws->timer, cs, K_MARCH)) != hipSuccess) return e;
-                if (fkind != march::F_HEART)
-                    wf_march<march::F_ANY><<<march_blocks, 256, 0, cs>>>(A, it, nullptr, march_slice);
-                else if (ws->diag)
-                    wf_march<march::F_HEART><<<march_blocks, 256, 0, cs>>>(A, it, ws->diag, march_slice);
-                else
-                    wf_march<march::F_HEART><<<march_blocks, 256, 0, cs>>>(A, it, nullptr, march_slice);
-                if ((e = hipGetLastError()) != hipSuccess) return e;
-                if ((e = timer_end(ws->timer, cs)) != hipSuccess) return e;
+                e = timed(ws->timer, cs, K_MARCH, [&] { launch_march(cs, A, it, ws->diag, fkind, march_slice); });
+                if (e != hipSuccess) return e;
             }
         }
         // the per-pixel sums take the chunks in sample order (chunk_list order)
         for (size_t c = r0; c < r1; c++) {
-            const Chunk &ch = chunk_list[c];
-            const int j = ch.slot;
-            const hipStream_t cs = j == 0 ? st : ws->side[j - 1];
+            const plan::Chunk &ch = chunk_list[c];
+            const hipStream_t cs = slot_stream(ws, st, ch.slot);
             const WfArgs *A = ad + 2 * c;
             const uint32_t npix = ch.gt * TILE * TILE;
             // a chunk of few pixels unwinds its slots first, one thread each (a thread per pixel would be one wave
@@ -1592,31 +1548,15 @@ static hipError_t render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
             // (profiles/r6/ab/r6m_reduce_split_summary.txt, r6q_unwind_all_summary.txt)
             const bool unwound = npix < UNWIND_PIXELS;
             if (unwound) {
-                const uint32_t slots_c = ch.ns * npix;
-                if ((e = timer_begin(ws->timer, cs, K_UNWIND)) != hipSuccess) return e;
-                if (sc.ext)
-                    wf_unwind<true><<<(slots_c + 255) / 256, 256, 0, cs>>>(A);
-                else
-                    wf_unwind<false><<<(slots_c + 255) / 256, 256, 0, cs>>>(A);
-                if ((e = hipGetLastError()) != hipSuccess) return e;
-                if ((e = timer_end(ws->timer, cs)) != hipSuccess) return e;
+                e = timed(ws->timer, cs, K_UNWIND, [&] { launch_unwind(ch.ns * npix, cs, sc, A); });
+                if (e != hipSuccess) return e;
             }
             if (slots > 1 && c > 0 && (e = hipStreamWaitEvent(cs, ws->reduced, 0)) != hipSuccess) return e;
-            if ((e = timer_begin(ws->timer, cs, K_REDUCE)) != hipSuccess) return e;
             // first: 1 = sums from zero, 2 = from out's running sums; last: 1 = means, 2 = running sums to out
             const int first = ch.s0 == s_begin ? (s_begin == 0 ? 1 : 2) : 0;
             const int last = ch.s0 + ch.ns >= s_end ? (s_end == P0.spp ? 1 : 2) : 0;
-            const uint32_t rb = (npix + 255) / 256;
-            if (sc.ext && unwound)
-                wf_reduce<true, true><<<rb, 256, 0, cs>>>(A, first, last, out);
-            else if (sc.ext)
-                wf_reduce<true, false><<<rb, 256, 0, cs>>>(A, first, last, out);
-            else if (unwound)
-                wf_reduce<false, true><<<rb, 256, 0, cs>>>(A, first, last, out);
-            else
-                wf_reduce<false, false><<<rb, 256, 0, cs>>>(A, first, last, out);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            if ((e = timer_end(ws->timer, cs)) != hipSuccess) return e;
+            e = timed(ws->timer, cs, K_REDUCE, [&] { launch_reduce(npix, cs, sc, A, unwound, first, last, out); });
+            if (e != hipSuccess) return e;
             if (slots > 1 && (e = hipEventRecord(ws->reduced, cs)) != hipSuccess) return e;
         }
         r0 = r1;
@@ -1656,12 +1596,5 @@ extern "C" int pt_march_regions(unsigned long long *out, int clear) {
     return 0;
 }
 #endif
-
-hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P, double *out, hipStream_t st,
-                              WaveWorkspace *ws, int fkind) {
-    if (P.tile_count == 0 || P.spp == 0) return hipSuccess;
-    // (the wavefront keeps attenuation ids in HBM, so one build serves every depth)
-    return render_wave(sc, P, out, st, ws, fkind);
-}
 
 }  // namespace pt

@@ -47,7 +47,7 @@ def _every_pixel(img, ref):
 def test_c2_multichunk_two_streams_every_pixel(pt, cornell_text):
     """The timed frame's structure at the headline size: several sample chunks
     on two chunk streams, per-pixel sums chained across the streams in chunk
-    order (pt_wave.hip render_wave_nw) — here 4 chunks of 2 spp (wf_paths =
+    order (pt_wave.hip launch_render_wave) — here 4 chunks of 2 spp (wf_paths =
     2^22) in two rounds of the 2 streams — every pixel against the oracle
     (src/renderer/mod.rs:151-155: the in-order per-pixel sum)."""
     import torch

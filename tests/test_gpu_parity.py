@@ -239,9 +239,29 @@ def test_wavefront_chunks_and_tile_groups(pt, cornell):
         img, ref = render_pair(pt, cornell, 70, 45, 2, 8, seed=10, wf_paths=256 * 7, wf_slots=slots)
         check_image(img, ref)
     # uneven sample chunks: 6 tiles, 2 spp per chunk at most, 5 spp -> 3 chunks,
-    # rounded up to 4 for two streams and balanced to 2, 1, 1, 1 samples
+    # rounded up to 4 for two streams and balanced to 1, 1, 1, 2 samples (tests/test_wave_plan.py)
     img, ref = render_pair(pt, cornell, 37, 21, 5, 8, seed=12, wf_paths=256 * 6 * 2, wf_slots=2)
     check_image(img, ref)
+
+
+def test_wavefront_launches_follow_the_plan(pt, cornell):
+    """The launches of one frame are the ones its plan implies (tests/test_wave_plan.py, 37x21 at 3 spp with 300
+    path slots): 6 one-tile groups x 3 one-sample chunks = 18 chunks, each with depth + 2 = 10 bounces, 9 select
+    and march rounds between them, and, being a chunk of few pixels, an unwind before its reduce."""
+    import torch
+    ps, osc = cornell
+    w, h, spp, depth, seed = 37, 21, 3, 8, 9
+    r = pt.HipRenderer(ps, depth=depth)
+    r.set_option("engine", 2)  # wavefront
+    r.set_option("wf_paths", 300)
+    frame = torch.zeros(w * h * 3, dtype=torch.float64, device="cuda")
+    pt.kernel_timing(r, True)
+    r.render_device(ps.camera(), w, h, spp, seed, 0, 1, frame.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    kt = pt.kernel_timing(r, False)
+    assert {k: n for k, (_, n) in kt.items()} == {"reduce": 18, "unwind": 18, "bounce": 180, "select": 162,
+                                                  "march": 162, "walk": 0, "megakernel": 0}
+    check_image(frame.view(-1, 3).cpu().numpy(), osc.render(w, h, spp, depth, seed))
 
 
 def test_wavefront_deep_paths(pt, spheres, cornell):
