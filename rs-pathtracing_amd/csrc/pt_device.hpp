@@ -873,6 +873,16 @@ struct IdStack {
     }
 };
 
+// The two ends of a path that shade() decides from (who, depth) alone, before it reads the scene: a miss ends with
+// background(ray.d) at any depth, and a hit at depth 0 ends black (mod.rs:24-27, 42-44).  In both cases shade()
+// writes *leaf and returns true, and touches nothing else: no random number is drawn, nothing is pushed, and the
+// ray, the depth and the stack stay as they were.  The wavefront engine rests on this: wf_bounce ends such a path
+// in the launch that traced its ray (when no march is pending that could still find a hit) with decided_leaf,
+// instead of carrying it to the next launch's shade.  tests/test_shade_miss.py pins it on the CPU.
+PT_HD bool shade_decided(int who, uint32_t depth) { return depth == 0 || who < 0; }
+// the leaf of a path shade_decided names: the background after a miss, black after a hit (at depth 0)
+PT_HD V3 decided_leaf(int who, const Ray &ray) { return who >= 0 ? v3(0.0, 0.0, 0.0) : background(ray.d); }
+
 // One bounce of ray_color (src/renderer/mod.rs:23-45).  Returns true when the
 // path ends, with the leaf radiance in *leaf; otherwise advances ray/depth.
 // Everything in a bounce after the closest hit (who, t) is known.

@@ -144,6 +144,7 @@ enum Point : int {
     PRE_SLAB,     // march pre-check: the ray enters a marched shape's padded box
     PRE_JOB,      // march pre-check: a march job record and its queue-order prediction
     ANY_END,      // a depth-0 trace that ends its path (any-hit answer)
+    MISS_END,     // a miss above depth 0 with no march pending, ended by the launch that traced it
     STORE,        // the state stores of every input position
     N_POINTS
 };

@@ -14,8 +14,11 @@
 //                  scatter, next ray — or end the path and store its sample
 //                  radiance), then trace the new ray through the uniform list
 //                  and the BVH.  A path whose ray enters a marched shape's
-//                  bound before its best hit goes to the march queue; the rest
-//                  go straight to the next live list.
+//                  bound before its best hit goes to the march queue.  A path
+//                  whose new ray hits nothing, with no march pending, ends
+//                  here with the background (as does any decided path at
+//                  depth 0): the next shade would do nothing else with it.
+//                  The rest go straight to the next live list.
 //   wf_march(it)   persistent lanes that refill themselves from the march
 //                  queue: every lane of every wave marches (select + march
 //                  iterations, pt_march.hpp) until the queue is drained, so
@@ -363,8 +366,10 @@ __global__ __launch_bounds__(256, WAVES) void wf_bounce(const WfArgs *__restrict
             }
         }
         // One bounce of this path: shade the pending hit (the camera ray has
-        // none), trace the new ray, and find whether a marched shape's bound
-        // starts before its best hit.  (Up to 2-3 bounces per launch for paths
+        // none), trace the new ray, find whether a marched shape's bound
+        // starts before its best hit, and end the path if the trace already
+        // decides it (a miss, or depth 0, with no march pending; SPLIT builds:
+        // wf_walk traces, nothing ends here).  (Up to 2-3 bounces per launch for paths
         // needing no march measured +0.8 % / -2.5 %, round 2.)
         bool need_march = false, long_job = false;
         V3 jo_o = dev::v3(0.0, 0.0, 0.0), jo_d = jo_o;  // a march job: the object-space ray and bound interval
@@ -413,12 +418,15 @@ __global__ __launch_bounds__(256, WAVES) void wf_bounce(const WfArgs *__restrict
                                                       jo_d.z, &jo_st, &jo_en);
             }
             PT_BSTAMP(5)
-            if (any && !need_march) {
-                PT_LP(ANY_END);
-                // its shade would end it at once (mod.rs:24-27, 42-44): black
-                // after a hit, the background after a miss; only paths whose
-                // answer needs a march go on to the last iteration
-                end_path(v, id, stk, who >= 0 ? dev::v3(0.0, 0.0, 0.0) : dev::background(ray.d));
+            if (!need_march && dev::shade_decided(who, depth)) {
+                // the next launch's shade would end it at once and touch nothing else (dev::shade_decided;
+                // mod.rs:24-27, 42-44): the background after a miss at any depth, black after a hit at depth 0.
+                // The path ends here, with the leaf and stack count that shade would have stored, and drops out
+                // of the wave's output below: no state, no status, no list entry, no lane of the next launch.
+                // Only paths whose answer needs a march go on undecided.
+                if (any) PT_LP(ANY_END);
+                else PT_LP(MISS_END);
+                end_path(v, id, stk, dev::decided_leaf(who, ray));
                 live = false;
             }
         }

@@ -18,11 +18,13 @@ import torch
 
 NAMES = ["live", "shade_hit", "lambert", "reject_try", "metal", "dielectric", "emit", "ended", "trace",
          "ulist_shape", "rect_rows", "ubox_pass", "bvh_node", "bvh_enter", "bvh_leaf", "pre_slab", "pre_job",
-         "any_end", "store"]
+         "any_end", "miss_end", "store"]
 L = pt.lib()
 f = L.pt_lane_prof
 f.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
 n = f(None, 0)
+if n == len(NAMES) - 1:  # a baseline library from before the miss_end point
+    NAMES.remove("miss_end")
 assert n == len(NAMES), (n, len(NAMES))
 spp = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 scene = sys.argv[2] if len(sys.argv) > 2 else "cornell_box.json"
