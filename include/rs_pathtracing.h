@@ -139,7 +139,16 @@ int pt_camera_new(const double position[3], const double direction[3], const dou
 /* ---- renderer: trait Renderer (src/renderer/mod.rs:47-56) -------------- */
 /* ThreadPoolRenderer::new(scene, thread_number, depth)
  * (src/renderer/step_by_step.rs:37): `device` (HIP ordinal, -1 = current)
- * replaces thread_number.  The scene must outlive the renderer. */
+ * replaces thread_number.  The scene must outlive the renderer.
+ * depth: any value up to PT_MAX_DEPTH, as the reference takes any u32 (its
+ * own recursion does not survive arbitrarily large ones); above it the create
+ * calls return PT_ERR_UNSUPPORTED with a message naming the limit.  A frame
+ * of depth > 64 always runs the wavefront engine's generic kernels and keeps
+ * (depth + 1) * 4 bytes of id stack per path in flight ((depth + 1) * 28 in a
+ * textured scene); when the device's free memory cannot hold that workspace
+ * even at the smallest chunks on one stream, the render call returns PT_ERR_UNSUPPORTED
+ * and pt_last_error says what was needed and what was available. */
+#define PT_MAX_DEPTH 4096
 int pt_renderer_create(pt_scene *scene, int device, uint32_t depth, pt_renderer **out);
 /* The same constructor with the parallelism knob spread over GPUs (the
  * thread_number of step_by_step.rs:37 -> ngpu): devices[0..ngpu) are HIP
@@ -284,11 +293,14 @@ int pt_checkpoint_load(const char *path, pt_checkpoint *c, double *sums, uint64_
 int pt_closest_hit(pt_renderer *r, const double *rays, size_t n, double min_t, double max_t,
                    pt_hit *out);
 /* ray_color (src/renderer/mod.rs:23-45) for n rays; rng_states[i] is the
- * stream state for ray i and is advanced in place. */
+ * stream state for ray i and is advanced in place.  depth <= PT_MAX_DEPTH
+ * (above 64 the id stacks live in device memory: n * depth * 4 bytes). */
 int pt_ray_color(pt_renderer *r, const double *rays, uint64_t *rng_states, size_t n, uint32_t depth,
                  double *out);
 /* trace_pixel_samples (src/renderer/mod.rs:151-155) for an explicit list of
- * pixel indices (x + y*w); out is n*3 means. */
+ * pixel indices (x + y*w); out is n*3 means.  Renderers of depth <= 64 only
+ * (PT_ERR_UNSUPPORTED above, naming the call: this probe and pt_count_work
+ * run the register id stacks; pt_profile_phases takes depth <= 8). */
 int pt_trace_pixel_samples(pt_renderer *r, const pt_camera *camera, uint32_t width, uint32_t height,
                            uint32_t samples_number, uint64_t seed, const uint32_t *pixels, size_t n,
                            double *out);

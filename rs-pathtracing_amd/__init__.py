@@ -36,6 +36,7 @@ PT_ERR_INVALID, PT_ERR_PARSE, PT_ERR_UNSUPPORTED, PT_ERR_HIP, PT_ERR_STATE, PT_E
 SPHERE, RECTANGLE, CUBE, MARCH, TORUS = 0, 1, 2, 3, 4
 LAMBERTIAN, METAL, DIELECTRIC, DIFFUSE_LIGHT, EMPTY = 0, 1, 2, 3, 4
 TILE = 16
+MAX_DEPTH = 4096  # PT_MAX_DEPTH: the largest depth a renderer or ray_color takes (PT_ERR_UNSUPPORTED above)
 
 # every symbol include/rs_pathtracing.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -318,7 +319,8 @@ class HipRenderer(Renderer):
     with HIP devices in place of the thread pool.  `device` is one HIP ordinal
     (-1 = current); `devices` (a list of ordinals, may repeat) spreads the
     frame's tiles over several (pt_renderer_create_multi).  `seed` keys the
-    per-(pixel, sample) RNG; render_step(blocking=False) is step_by_step's
+    per-(pixel, sample) RNG; `depth` is any value up to MAX_DEPTH (frames deeper than 64 run the wavefront
+    engine's generic kernels); render_step(blocking=False) is step_by_step's
     non-blocking drain, blocking=True is thread_pool_new's."""
 
     def __init__(self, scene: Scene, device: int = -1, depth: int = 50, seed: int = 1, devices=None):

@@ -21,6 +21,7 @@
 #include "../../include/rs_pathtracing.h"
 #include "pt_accel.hpp"
 #include "pt_kernel.hpp"
+#include "pt_plan.hpp"
 #include "pt_scene.hpp"
 
 using namespace pt;
@@ -40,6 +41,22 @@ int hip_fail(hipError_t e, const char *what) {
         hipError_t e_ = (expr);                        \
         if (e_ != hipSuccess) return hip_fail(e_, #expr); \
     } while (0)
+
+static_assert(PT_MAX_DEPTH == plan::MAX_DEPTH, "the header states the plan's depth limit");
+// the depth limit of the create calls and pt_ray_color
+int depth_refused(uint32_t depth) {
+    if (depth <= PT_MAX_DEPTH) return PT_OK;
+    return fail(PT_ERR_UNSUPPORTED, "depth " + std::to_string(depth) + " is above the largest supported depth, " +
+                                        std::to_string(PT_MAX_DEPTH) + " (PT_MAX_DEPTH)");
+}
+// the calls that run the register id stacks only (64 ids)
+int reg_depth_refused(uint32_t depth, const char *call) {
+    if (depth <= MAX_REG_DEPTH) return PT_OK;
+    return fail(PT_ERR_UNSUPPORTED, std::string(call) + " supports depth <= " + std::to_string(MAX_REG_DEPTH) +
+                                        " (the renderer's depth is " +
+                                        std::to_string(depth) + "); frames and pt_ray_color take any depth up to " +
+                                        std::to_string(PT_MAX_DEPTH));
+}
 
 uint32_t tiles_x_of(uint32_t w) { return (w + TILE - 1) / TILE; }
 uint32_t tiles_y_of(uint32_t h) { return (h + TILE - 1) / TILE; }
@@ -478,6 +495,15 @@ void rank_range(uint32_t a, uint32_t b, uint32_t rank, uint32_t world, uint32_t 
     *i1 = b > rank ? (b - rank + world - 1) / world : 0;
 }
 
+// launch_render on g's device: a refusal (WaveWorkspace::refusal: a deep frame whose workspace does not fit) is
+// PT_ERR_UNSUPPORTED with its message, anything else a HIP failure.
+int render_on(GpuShare &g, const FrameParams &P, double *dst, hipStream_t st) {
+    const hipError_t e = launch_render(g.ds, P, dst, st, &g.ws);
+    if (e == hipSuccess) return PT_OK;
+    if (g.ws.refusal[0]) return fail(PT_ERR_UNSUPPORTED, g.ws.refusal);
+    return hip_fail(e, "launch_render");
+}
+
 template <class T>
 int grow(T **p, size_t *cap, size_t n) {
     const size_t bytes = n * sizeof(T);
@@ -533,7 +559,7 @@ int enqueue_band(pt_renderer *r, const FrameParams &P0, double *d_frame, uint8_t
         P.tile_begin = i0;
         P.tile_count = i1 - i0;
         double *dst = world == 1 ? d_frame : (k == 0 ? r->d_gather : g.d_shard);
-        HIP_TRY(launch_render(g.ds, P, dst, g.stream, &g.ws));
+        if (int rc = render_on(g, P, dst, g.stream)) return rc;
         if (k > 0) {
             if (i1 > i0) {
                 const size_t off = (size_t)i0 * TILE * TILE * 3, n = (size_t)(i1 - i0) * TILE * TILE * 3;
@@ -614,7 +640,7 @@ int enable_peers(pt_renderer *r) {
 
 int create_renderer(pt_scene *scene, const std::vector<int> &devices, uint32_t depth, pt_renderer **out) {
     *out = nullptr;
-    if (depth > 64) return fail(PT_ERR_UNSUPPORTED, "depth > 64 is not supported on the GPU path");
+    if (int rc = depth_refused(depth)) return rc;
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count == 0) return fail(PT_ERR_HIP, "no HIP device available (the GPU path has no CPU fallback)");
@@ -941,7 +967,7 @@ int pt_render_device_samples(pt_renderer *r, const pt_camera *cam, uint32_t w, u
     // any HIP stream of the renderer's (first) device, 0 being the null stream
     // as everywhere in HIP (pt_unshard_device takes the same handle, so a
     // caller's render -> gather -> unshard stays ordered)
-    HIP_TRY(launch_render(g.ds, P, d_out, (hipStream_t)stream, &g.ws));
+    if (int rc = render_on(g, P, d_out, (hipStream_t)stream)) return rc;
     return PT_OK;
 }
 
@@ -1000,7 +1026,7 @@ int pt_closest_hit(pt_renderer *r, const double *rays, size_t n, double min_t, d
 
 int pt_ray_color(pt_renderer *r, const double *rays, uint64_t *states, size_t n, uint32_t depth, double *out) {
     if (!r || (n && (!rays || !states || !out))) return fail(PT_ERR_INVALID, "null argument");
-    if (depth > 64) return fail(PT_ERR_UNSUPPORTED, "depth > 64 is not supported on the GPU path");
+    if (int rc = depth_refused(depth)) return rc;
     HIP_TRY(hipSetDevice(r->device()));
     DevBuf<double> dr, dout;
     DevBuf<uint64_t> ds;
@@ -1022,6 +1048,7 @@ int pt_trace_pixel_samples(pt_renderer *r, const pt_camera *cam, uint32_t w, uin
     if (w == 0 || h == 0 || spp == 0) return fail(PT_ERR_INVALID, "width, height and samples_number must be > 0");
     for (size_t i = 0; i < n; i++)
         if (pixels[i] >= (uint64_t)w * h) return fail(PT_ERR_INVALID, "pixel index out of range");
+    if (int rc = reg_depth_refused(r->depth, "pt_trace_pixel_samples")) return rc;
     HIP_TRY(hipSetDevice(r->device()));
     FrameParams P = frame_params(r, *cam, w, h, spp, seed);
     DevBuf<uint32_t> dp;
@@ -1042,6 +1069,7 @@ int pt_count_work(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, 
     if (w == 0 || h == 0 || spp == 0) return fail(PT_ERR_INVALID, "width, height and samples_number must be > 0");
     for (size_t i = 0; i < n; i++)
         if (pixels[i] >= (uint64_t)w * h) return fail(PT_ERR_INVALID, "pixel index out of range");
+    if (int rc = reg_depth_refused(r->depth, "pt_count_work")) return rc;
     HIP_TRY(hipSetDevice(r->device()));
     FrameParams P = frame_params(r, *cam, w, h, spp, seed);
     DevBuf<uint32_t> dp;

@@ -996,6 +996,48 @@ PT_HD V3 ray_color(const Scene &sc, Ray ray, uint32_t depth, Rng &rng, double s1
     return unwind<false, EXT>(sc, stk, leaf);
 }
 
+// The attenuation stack of one path in memory, for depths beyond IdStack's registers (depth > 64): id k at
+// ids[k * stride], a textured value of level k, component c at vb[(k * 3 + c) * stride] (EXT builds).  The caller
+// provides `depth` ids (a path pushes at most one per bounce) and depth levels of values.
+struct MemIdStack {
+    uint32_t *ids;
+    double *vb;
+    size_t stride;
+    int n;
+    PT_HD void push_val(V3 a) {
+        vb[((size_t)n * 3 + 0) * stride] = a.x;
+        vb[((size_t)n * 3 + 1) * stride] = a.y;
+        vb[((size_t)n * 3 + 2) * stride] = a.z;
+        push(VAL_BIT);
+    }
+    PT_HD V3 val(int level) const {
+        return v3(vb[((size_t)level * 3 + 0) * stride], vb[((size_t)level * 3 + 1) * stride],
+                  vb[((size_t)level * 3 + 2) * stride]);
+    }
+    PT_HD void push(uint32_t id) {
+        ids[(size_t)n * stride] = id;
+        n++;
+    }
+    PT_HD uint32_t pop() {
+        n--;
+        return ids[(size_t)n * stride];
+    }
+};
+
+// ray_color with the stack in memory: the same bounces and the same product order as ray_color<NW>, at any depth.
+template <bool EXT = false>
+PT_HD V3 ray_color_mem(const Scene &sc, Ray ray, uint32_t depth, Rng &rng, double s11, uint32_t *ids, double *vb,
+                       size_t stride) {
+    MemIdStack stk{ids, vb, stride, 0};
+    V3 leaf;
+    for (;;) {
+        double t;
+        const int who = closest<false, EXT>(sc, ray, T_MIN, __builtin_inf(), &t);
+        if (shade<false, march::F_ANY, EXT>(sc, who, t, ray, depth, stk, rng, s11, &leaf)) break;
+    }
+    return unwind<false, EXT>(sc, stk, leaf);
+}
+
 // Camera sample: MultisamplerRayCaster::next (ray_caster.rs:103-118), u then v.
 PT_HD Ray camera_ray(const FrameParams &P, uint32_t x, uint32_t y, Rng &rng) {
     double u = rng.gen();

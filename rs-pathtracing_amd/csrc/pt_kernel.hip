@@ -134,6 +134,26 @@ __global__ __launch_bounds__(256) void ray_color_probe(dev::Scene sc, const doub
     out[i * 3 + 2] = c.z;
 }
 
+// The probe at depths beyond the register stacks (depth > MAX_REG_DEPTH): the id stack in memory, lane i's id k at
+// ids[k * n + i] (dev::MemIdStack), the same bounces and product order.
+template <bool EXT>
+__global__ __launch_bounds__(256) void ray_color_probe_deep(dev::Scene sc, const double *__restrict__ rays,
+                                                            uint64_t *__restrict__ states, size_t n, uint32_t depth,
+                                                            double s11, double *__restrict__ out, uint32_t *ids,
+                                                            double *vals) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Ray r;
+    r.o = dev::v3(rays[i * 6 + 0], rays[i * 6 + 1], rays[i * 6 + 2]);
+    r.d = dev::v3(rays[i * 6 + 3], rays[i * 6 + 4], rays[i * 6 + 5]);
+    dev::Rng rng{states[i]};
+    V3 c = dev::ray_color_mem<EXT>(sc, r, depth, rng, s11, ids + i, EXT ? vals + i : nullptr, n);
+    states[i] = rng.s;
+    out[i * 3 + 0] = c.x;
+    out[i * 3 + 1] = c.y;
+    out[i * 3 + 2] = c.z;
+}
+
 template <int NW>
 __global__ __launch_bounds__(256) void trace_pixels_probe(dev::Scene sc, FrameParams P, const uint32_t *__restrict__ pixels, size_t n,
                                    double *__restrict__ out, double *vals) {
@@ -256,7 +276,10 @@ static dev::Scene dscene(const DeviceScene &s) {
     return d;
 }
 
-// Attenuation-stack width by depth: one 32-bit material id per bounce.
+// Attenuation-stack width by depth: one 32-bit material id per bounce.  The widest build holds MAX_REG_DEPTH ids
+// (pt_kernel.hpp): every launcher below sends a deeper call elsewhere (the wavefront engine, the memory-stack probe)
+// or refuses it.
+static_assert(MAX_REG_DEPTH == 2 * 32, "IdStack<32> holds 64 ids");
 #define PT_DISPATCH_NW(depth, CALL)        \
     do {                                   \
         if ((depth) <= 8) {                \
@@ -362,6 +385,14 @@ static bool use_wavefront(const DeviceScene &s, const FrameParams &P, WaveWorksp
 hipError_t launch_render(const DeviceScene &s, const FrameParams &P, double *out, hipStream_t st,
                          WaveWorkspace *ws) {
     if (P.tile_count == 0) return hipSuccess;
+    if (ws) ws->refusal[0] = 0;
+    if (P.depth > MAX_REG_DEPTH) {
+        // a deep frame: the wavefront engine's id stacks live in memory; whatever `engine` says and however small the
+        // frame, and never the megakernel
+        const bool window = P.s_begin > 0 || (P.s_end && P.s_end < P.spp);
+        if (!ws || (window && P.s_begin >= (P.s_end ? P.s_end : P.spp))) return hipErrorInvalidValue;
+        return launch_render_wave(dscene(s), P, out, st, ws, s.fkind);
+    }
     if (P.s_begin > 0 || (P.s_end && P.s_end < P.spp)) {
         // a sample window: only the wavefront engine keeps running sums across launches
         if (!ws || P.s_begin >= (P.s_end ? P.s_end : P.spp)) return hipErrorInvalidValue;
@@ -423,9 +454,20 @@ struct ProbeVals {
     hipStream_t st;
     hipError_t alloc(const DeviceScene &s, size_t n, uint32_t depth) {
         if (!s.ext) return hipSuccess;
-        return hipMallocAsync((void **)&p, n * (depth + 1) * 3 * sizeof(double), st);
+        return hipMallocAsync((void **)&p, n * ((size_t)depth + 1) * 3 * sizeof(double), st);
     }
     ~ProbeVals() {
+        if (p) (void)hipFreeAsync(p, st);
+    }
+};
+// The same for a deep probe's id stacks: n lanes x depth ids.
+struct ProbeIds {
+    uint32_t *p = nullptr;
+    hipStream_t st;
+    hipError_t alloc(size_t n, uint32_t depth) {
+        return hipMallocAsync((void **)&p, n * (size_t)depth * sizeof(uint32_t), st);
+    }
+    ~ProbeIds() {
         if (p) (void)hipFreeAsync(p, st);
     }
 };
@@ -436,6 +478,16 @@ hipError_t launch_ray_color(const DeviceScene &s, const double *rays, uint64_t *
     ProbeVals vals{nullptr, st};
     hipError_t e = vals.alloc(s, n, depth);
     if (e != hipSuccess) return e;
+    if (depth > MAX_REG_DEPTH) {
+        ProbeIds ids{nullptr, st};
+        if ((e = ids.alloc(n, depth)) != hipSuccess) return e;
+        const unsigned blocks = (unsigned)((n + 255) / 256);
+        if (s.ext)
+            ray_color_probe_deep<true><<<blocks, 256, 0, st>>>(dscene(s), rays, states, n, depth, s11, out, ids.p, vals.p);
+        else
+            ray_color_probe_deep<false><<<blocks, 256, 0, st>>>(dscene(s), rays, states, n, depth, s11, out, ids.p, nullptr);
+        return hipGetLastError();
+    }
     PT_DISPATCH_NW(depth, (ray_color_probe<NW><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(
                               dscene(s), rays, states, n, depth, s11, out, vals.p)));
     return hipGetLastError();
@@ -444,6 +496,7 @@ hipError_t launch_ray_color(const DeviceScene &s, const double *rays, uint64_t *
 hipError_t launch_trace_pixels(const DeviceScene &s, const FrameParams &P, const uint32_t *pixels, size_t n,
                                double *out, hipStream_t st) {
     if (!n) return hipSuccess;
+    if (P.depth > MAX_REG_DEPTH) return hipErrorNotSupported;  // (register id stacks only)
     ProbeVals vals{nullptr, st};
     hipError_t e = vals.alloc(s, n, P.depth);
     if (e != hipSuccess) return e;
@@ -455,6 +508,7 @@ hipError_t launch_trace_pixels(const DeviceScene &s, const FrameParams &P, const
 hipError_t launch_count_work(const DeviceScene &s, const FrameParams &P, const uint32_t *pixels, size_t n,
                              unsigned long long *ctr, hipStream_t st) {
     if (!n) return hipSuccess;
+    if (P.depth > MAX_REG_DEPTH) return hipErrorNotSupported;  // (register id stacks only)
     ProbeVals vals{nullptr, st};
     hipError_t e = vals.alloc(s, n, P.depth);
     if (e != hipSuccess) return e;

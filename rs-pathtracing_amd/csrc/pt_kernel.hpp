@@ -26,6 +26,10 @@ struct DeviceScene {
     unsigned long long *guard = nullptr;  // device counter of marches dropped by the march guard
 };
 
+// The deepest call the register id stacks take (IdStack<32>: the megakernel, trace_pixels_probe, count_work and
+// ray_color_probe).  Deeper frames run the wavefront engine, deeper pt_ray_color calls the memory-stack probe.
+constexpr uint32_t MAX_REG_DEPTH = 64;
+
 // Per-kernel launch timing (pt_kernel_timing): HIP events recorded on the
 // launch stream around every render-path kernel while enabled.
 // (kind 5 was the wavefront tail kernel until round 6; it now times the per-slot unwind, wf_unwind)
@@ -94,12 +98,16 @@ struct WaveWorkspace {
     hipEvent_t args_ev = nullptr;
     bool args_pending = false;
     int device = -1;
+    // why launch_render refused the last frame without a HIP failure (empty: it did not): a frame whose workspace
+    // the device cannot hold (pt_wave.hip launch_render_wave)
+    char refusal[320] = {};
 };
 void wave_workspace_free(WaveWorkspace *ws);
 
 // Renders this rank's tiles of P into out.  Scenes with ray-marched shapes use
 // the wavefront engine (ws required), others the megakernel; the renderer
-// option "engine" (1 megakernel, 2 wavefront) forces one.
+// option "engine" (1 megakernel, 2 wavefront) forces one.  A frame of depth > 64 always takes the wavefront engine
+// (the megakernel's register id stack holds 64 ids).  An error with ws->refusal set is a refusal, not a HIP failure.
 hipError_t launch_render(const DeviceScene &s, const FrameParams &P, double *out, hipStream_t st,
                          WaveWorkspace *ws);
 // rows [y0, y1) of the frame from gathered shards (pt_unshard_device)

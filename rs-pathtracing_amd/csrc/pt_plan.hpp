@@ -18,6 +18,21 @@ constexpr uint32_t MIN_CHUNK_PATHS = 1u << 21;
 constexpr size_t RESERVE_BYTES = (size_t)2 << 30;
 // Input::avail_bytes when the device's free memory is unknown: the plan is not shrunk to fit.
 constexpr size_t MEM_UNKNOWN = ~(size_t)0;
+// The largest depth a renderer takes (PT_MAX_DEPTH in rs_pathtracing.h).  Every product below is in size_t, which
+// must be 64 bits: at this depth a path's id stack alone is 16 KiB, a chunk of 2^28 paths 4 TiB (the fit then halves
+// it), iters is 4098 and cnt_words 16400.
+constexpr uint32_t MAX_DEPTH = 4096;
+static_assert(sizeof(size_t) >= 8, "the region sizes are 64-bit products");
+static_assert((uint64_t)MAX_DEPTH + 4 < (1u << 28), "iters and cnt_words fit an int");
+static_assert(((uint64_t)1 << 32) * 24 * ((uint64_t)MAX_DEPTH + 1) < ((uint64_t)1 << 62), "cap * 24 * (depth + 1)");
+// Frames deeper than this keep the attenuation-stack count outside the path's who word, whose 7 spare bits hold
+// counts up to 64 only (pt_wave.hip pack_who): in the spare top level of the slot's id stack, ids[depth * cap + id]
+// (R_IDS has depth + 1 levels and a path pushes at most depth ids).  No region changes size.
+constexpr uint32_t PACKED_COUNT_DEPTH = 64;
+constexpr bool deep(uint32_t depth) { return depth > PACKED_COUNT_DEPTH; }
+// The depths the plan is made for.  plan_for plans a larger one as MAX_DEPTH, so that no quantity below wraps
+// whatever a caller passes; launch_render_wave refuses such a frame before it plans.
+constexpr bool depth_ok(uint32_t depth) { return depth <= MAX_DEPTH; }
 
 // Path slots per chunk when Tuning::wf_paths is 0, by depth (deep frames: bigger chunks, fewer tails).
 // (deep frames: 256M paths, two chunks of a 1080p x 256-spp frame in one step, ~120 GB per chunk stream at depth
@@ -73,8 +88,9 @@ inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 inline Plan plan_for(const Input &in, uint32_t cap_want) {
     Plan pl;
     const uint32_t ntiles = in.ntiles, nsw = in.s_end - in.s_begin;
+    const uint32_t depth = depth_ok(in.depth) ? in.depth : MAX_DEPTH;
     pl.cap_want = cap_want;
-    pl.iters = (int)in.depth + 2;  // traces per path <= depth + 1, then one last shade
+    pl.iters = (int)depth + 2;  // traces per path <= depth + 1, then one last shade
     pl.cnt_words = (size_t)(pl.iters + 2) * 4;
     const uint32_t tiles_per_group = cap_want / (TILE * TILE) ? cap_want / (TILE * TILE) : 1;
     pl.group_tiles = ntiles < tiles_per_group ? ntiles : tiles_per_group;
@@ -105,7 +121,7 @@ inline Plan plan_for(const Input &in, uint32_t cap_want) {
     // a slot: two path-state sets, id stacks, 32-byte leaf records (end_path), live list and march queue,
     // statuses, the compaction's tile counts (CpLayout: 3 x per * 256 words), counters, textured attenuation
     // values, pre-selected march jobs
-    const size_t cap = pl.cap, d1 = in.depth + 1;
+    const size_t cap = pl.cap, d1 = (size_t)depth + 1;
     const size_t need[R_COUNT] = {cap * PATH_BYTES,
                                   cap * PATH_BYTES,
                                   cap * 4 * d1,
@@ -141,6 +157,28 @@ inline Plan make_plan(const Input &in) {
     while (pl.bytes > in.avail_bytes && cap_want > MIN_CHUNK_PATHS) {
         cap_want = cap_want / 2 > MIN_CHUNK_PATHS ? cap_want / 2 : MIN_CHUNK_PATHS;
         pl = plan_for(in, cap_want);
+    }
+    return pl;
+}
+
+// Whether the workspace of the plan fits what it may take (avail_bytes: the free memory less the reserve).
+// make_plan stops halving at MIN_CHUNK_PATHS, and the plan it returns then may still be too large (a very deep
+// textured frame: (depth + 1) * 28 B per path and slot).  The reserve is a margin for sizing chunks, not a limit: a
+// plan that does not fit in this sense is still run when the device can hold it (fits_device).
+inline bool fits(const Input &in, const Plan &pl) { return pl.bytes <= in.avail_bytes; }
+// Whether the device can hold the plan's workspace at all.  hard_bytes: what is free plus what the workspace holds
+// now, nothing kept back (or MEM_UNKNOWN); a workspace that already covers the plan always can.
+inline bool fits_device(const Plan &pl, size_t hard_bytes) { return pl.bytes <= hard_bytes; }
+
+// The plan launch_render_wave runs: make_plan's, whenever the device can hold it (so every frame that could be
+// allocated before is planned as before, the small frame on a nearly full device included).  Only when it cannot,
+// the plan is made once more for a single chunk stream (half the workspace); when fits_device still says no, the
+// caller refuses the frame.  *in is left as the plan was made from (chunk_list takes the same).
+inline Plan make_plan_fit(Input *in, size_t hard_bytes) {
+    Plan pl = make_plan(*in);
+    if (!fits_device(pl, hard_bytes) && in->wf_slots > 1) {
+        in->wf_slots = 1;
+        pl = make_plan(*in);
     }
     return pl;
 }

@@ -41,6 +41,7 @@
 // bit-identical.
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
 #include <cstdlib>
 #include <vector>
 
@@ -73,6 +74,9 @@ using dev::V3;
 // path; round 5): a live path's depth at bounce `it` is depth - (it - 1) for every path (each bounce before it
 // shaded it once and scattered), so only the stack count is state; it shares a word with the pending hit's
 // shape: (who + 1) | count << 25 (shapes < 2^24: the BVH's leaf index bound; count <= depth <= 64).
+// Deeper frames (plan::deep: the DEEP builds of wf_bounce) leave the count bits of the word 0 and keep the count in
+// the slot's id stack, at the level no push reaches: ids[depth * cap + id] (deep_count).  The march and the walk
+// carry the word's high bits through unchanged, whatever they hold; the leaf record's count is a full 32-bit value.
 constexpr uint32_t WHO_MASK = (1u << 25) - 1u;
 __host__ __device__ __forceinline__ uint32_t pack_who(int who, uint32_t count) {
     return (uint32_t)(who + 1) | (count << 25);
@@ -273,6 +277,13 @@ __device__ __forceinline__ void load_path(const PathSoA &S, uint32_t p, uint32_t
     *best = ld_path(a + PathSoA::T * B);
 }
 
+// launch_render sends the wavefront engine every frame the register stacks cannot take: exactly the DEEP ones
+static_assert(plan::PACKED_COUNT_DEPTH == MAX_REG_DEPTH, "the DEEP builds start where the register stacks end");
+// A deep frame's attenuation-stack count of slot id (R_IDS has depth + 1 levels, a path pushes at most depth ids).
+__device__ __forceinline__ uint32_t *deep_count(const WfView &v, uint32_t depth, uint32_t id) {
+    return v.ids + (size_t)depth * v.cap + id;
+}
+
 // Pixel of a path slot: slot = (s_local * tiles + ti_local) * 256 + thread-in-tile,
 // thread-in-tile laid out as render_tiles' 4 waves of 8x8.
 __device__ __forceinline__ void slot_pixel(const FrameParams &P, const WfView &v, uint32_t id, uint32_t *x,
@@ -300,7 +311,10 @@ constexpr int WF_PREDICT = 4;
 // stores; summed into diag[36..42].
 // SPLIT (the large-tree builds without marched shapes, C5): the kernel only shades and stores the new ray; wf_walk
 // traces it after the compaction (Tuning::wf_walk).
-template <bool FIRST, int WAVES, int FK = march::F_ANY, bool EXT = false, bool BIGBVH = false, bool SPLIT = false>
+// DEEP (frames of depth > 64, the generic builds only): the stack count lives in the slot's id stack (deep_count),
+// read after the slot id and written with the path's state.
+template <bool FIRST, int WAVES, int FK = march::F_ANY, bool EXT = false, bool BIGBVH = false, bool SPLIT = false,
+          bool DEEP = false>
 __global__ __launch_bounds__(256, WAVES) void wf_bounce(const WfArgs *__restrict__ A, int it,
                                                         unsigned long long *diag = nullptr) {
     // input: the id-sorted list of live paths (iteration 0: every slot)
@@ -360,7 +374,7 @@ __global__ __launch_bounds__(256, WAVES) void wf_bounce(const WfArgs *__restrict
                 // (every live path has been shaded it - 1 times, each a scatter: its depth is P.depth - (it - 1))
                 load_path(v.in, p, &id, &ray, &rng.s, P.depth + 1u - (uint32_t)it, &depth, &count, &who, &best);
                 stk.base = v.ids + id;
-                stk.n = (int)count;
+                stk.n = DEEP ? (int)*deep_count(v, P.depth, id) : (int)count;
                 if (EXT) stk.vb = v.att + id;
                 PT_BSTAMP(1)
             }
@@ -466,7 +480,8 @@ __global__ __launch_bounds__(256, WAVES) void wf_bounce(const WfArgs *__restrict
         }
         if (i < count) PT_LP(STORE);
         if (i < count && live) {
-            store_path(v.out, k, id, ray, best, who, rng.s, (uint32_t)stk.n);
+            store_path(v.out, k, id, ray, best, who, rng.s, DEEP ? 0u : (uint32_t)stk.n);
+            if (DEEP) *deep_count(v, P.depth, id) = (uint32_t)stk.n;
             v.status[k] = live ? (need_march ? (long_job ? 7u : 3u) : 1u) : 0u;
         }
         PT_BSTAMP(6)
@@ -1252,7 +1267,14 @@ static bool walk_split(const dev::Scene &sc, const Tuning &tu) {
 
 template <bool FIRST>
 static void launch_bounce_build(uint32_t blocks, hipStream_t st, const dev::Scene &sc, const WfArgs *A, int it,
-                          unsigned long long *diag, int fkind, int waves, bool split) {
+                          unsigned long long *diag, int fkind, int waves, bool split, bool deep) {
+    if (deep) {  // depth > 64: the generic builds with the stack count in the id stack, whatever the scene
+        if (sc.ext)
+            wf_bounce<FIRST, 2, march::F_ANY, true, false, false, true><<<blocks, 256, 0, st>>>(A, it);
+        else
+            wf_bounce<FIRST, 2, march::F_ANY, false, false, false, true><<<blocks, 256, 0, st>>>(A, it);
+        return;
+    }
     if (split) {  // shade and store the new ray only: wf_walk traces it
         switch (waves) {
         case 4: wf_bounce<FIRST, 4, march::F_NONE, false, true, true><<<blocks, 256, 0, st>>>(A, it); break;
@@ -1297,11 +1319,11 @@ static void launch_bounce_build(uint32_t blocks, hipStream_t st, const dev::Scen
 
 // The bounce of iteration it: the chunk's camera rays (first), or the live list of it.
 static void launch_bounce(bool first, uint32_t blocks, hipStream_t st, const dev::Scene &sc, const WfArgs *A, int it,
-                          unsigned long long *diag, int fkind, int waves, bool split) {
+                          unsigned long long *diag, int fkind, int waves, bool split, bool deep) {
     if (first)
-        launch_bounce_build<true>(blocks, st, sc, A, it, diag, fkind, waves, split);
+        launch_bounce_build<true>(blocks, st, sc, A, it, diag, fkind, waves, split, deep);
     else
-        launch_bounce_build<false>(blocks, st, sc, A, it, diag, fkind, waves, split);
+        launch_bounce_build<false>(blocks, st, sc, A, it, diag, fkind, waves, split, deep);
 }
 
 // The new rays' BVH walk, over the live list of it + 1 (walk_split scenes).
@@ -1418,10 +1440,30 @@ hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
     in.wf_min_chunks = tu.wf_min_chunks;
     // the workspace may take what is free plus what it holds now, less the reserve
     in.avail_bytes = plan::MEM_UNKNOWN;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-        in.avail_bytes = free_b + ws->bytes > plan::RESERVE_BYTES ? free_b + ws->bytes - plan::RESERVE_BYTES : 0;
-    const plan::Plan pl = plan::make_plan(in);
+    size_t free_b = 0, total_b = 0, hard_bytes = plan::MEM_UNKNOWN;  // hard_bytes: the same with nothing kept back
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+        hard_bytes = free_b + ws->bytes;
+        in.avail_bytes = hard_bytes > plan::RESERVE_BYTES ? hard_bytes - plan::RESERVE_BYTES : 0;
+    }
+    if (!plan::depth_ok(P0.depth)) {  // (the create calls refuse it first)
+        snprintf(ws->refusal, sizeof ws->refusal, "depth %u is above the largest supported depth, %u", P0.depth,
+                 plan::MAX_DEPTH);
+        return hipErrorInvalidValue;
+    }
+    // Every frame whose workspace the device can hold runs make_plan's plan, as before (the reserve is a margin for
+    // sizing chunks: a frame that does not fit inside it is still allocated, and one the workspace already covers
+    // allocates nothing).  A workspace the device cannot hold (a very deep frame at the smallest chunks: (depth + 1)
+    // * 28 B per textured path) is planned again with one chunk stream, and the frame is refused when the device
+    // cannot hold that either: the allocation could only fail.
+    const plan::Plan pl = plan::make_plan_fit(&in, hard_bytes);
+    if (!plan::fits_device(pl, hard_bytes)) {
+        // refused before any launch or allocation; the caller reports ws->refusal (PT_ERR_UNSUPPORTED)
+        snprintf(ws->refusal, sizeof ws->refusal,
+                 "the wavefront workspace does not fit the device: depth %u, %s scene, %u paths per chunk on %d "
+                 "stream(s) need %zu bytes, %zu bytes available",
+                 P0.depth, in.textured ? "textured" : "untextured", pl.cap, pl.slots, pl.bytes, hard_bytes);
+        return hipErrorOutOfMemory;
+    }
     const plan::Layout &L = pl.lay;
     const std::vector<plan::Chunk> chunk_list = plan::chunk_list(in, pl);
     const int slots = pl.slots, iters = pl.iters;
@@ -1456,7 +1498,10 @@ hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
     }
 
     const uint32_t march_slice = (uint32_t)tu.wf_march_slice;
-    const bool split = walk_split(sc, tu);
+    // a deep frame (depth > 64) runs the generic DEEP bounce builds: no wf_walk route, no Heart-only march
+    const bool deep = plan::deep(P0.depth);
+    const bool split = !deep && walk_split(sc, tu);
+    if (deep) fkind = -1;
     // The launches' argument blocks (WfArgs): chunk ci at iteration parity h is block 2 ci + h.  They are
     // written to the pinned staging buffer, which the previous frame's copy must have read, and copied to the
     // device on st after the previous frame's kernels (the wait on ws->done above), before the side streams fork.
@@ -1516,7 +1561,7 @@ hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
                 // iteration 0: slots [0, paths) are the chunk's camera rays
                 e = timed(ws->timer, cs, K_BOUNCE, [&] {
                     launch_bounce(it == 0, it == 0 ? (paths + 255) / 256 : bb, cs, sc, A, it, ws->diag, fkind,
-                                  tu.wf_bounce_waves, split);
+                                  tu.wf_bounce_waves, split, deep);
                 });
                 if (e != hipSuccess) return e;
                 if (it == iters - 1) continue;  // the last bounce only shades
