@@ -541,7 +541,7 @@ def option_names() -> list:
         i += 1
 
 
-# the defaults (pt_kernel.hpp Tuning): bench.py reports knobs that differ
+# the defaults (pt_builds.hpp Tuning): bench.py reports knobs that differ
 OPTION_DEFAULTS = {"engine": 0, "mega_waves": 4, "diag": 0, "wf_slots": 2, "wf_paths": 0, "wf_min_chunks": 1,
                    "wf_bounce_waves": 3, "wf_march_slice": 256, "wf_walk": 5, "bvh_leaf": 1}
 

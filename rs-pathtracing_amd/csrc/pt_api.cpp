@@ -498,7 +498,7 @@ void rank_range(uint32_t a, uint32_t b, uint32_t rank, uint32_t world, uint32_t 
 // launch_render on g's device: a refusal (WaveWorkspace::refusal: a deep frame whose workspace does not fit) is
 // PT_ERR_UNSUPPORTED with its message, anything else a HIP failure.
 int render_on(GpuShare &g, const FrameParams &P, double *dst, hipStream_t st) {
-    const hipError_t e = launch_render(g.ds, P, dst, st, &g.ws);
+    const hipError_t e = launch_render(g.ds, P, dst, st, g.ws);
     if (e == hipSuccess) return PT_OK;
     if (g.ws.refusal[0]) return fail(PT_ERR_UNSUPPORTED, g.ws.refusal);
     return hip_fail(e, "launch_render");
@@ -727,7 +727,7 @@ int pt_renderer_set_option(pt_renderer *r, const char *name, int64_t value) {
     if (!std::strcmp(name, "bvh_leaf") && value != r->gpus[0].ws.tune.bvh_leaf) {
         // the BVH is rebuilt with the new leaf size on every device
         Tuning t = r->gpus[0].ws.tune;
-        if (tuning_set(&t, name, value) != PT_OK)
+        if (!tuning_set(&t, name, value))
             return fail(PT_ERR_INVALID, "bvh_leaf out of range (1..16): " + std::to_string((long long)value));
         std::vector<StagedAccel> staged(r->gpus.size());
         auto drop = [&] {
@@ -758,7 +758,7 @@ int pt_renderer_set_option(pt_renderer *r, const char *name, int64_t value) {
     }
     for (auto &g : r->gpus) {
         Tuning t = g.ws.tune;
-        if (tuning_set(&t, name, value) != PT_OK)
+        if (!tuning_set(&t, name, value))
             return fail(PT_ERR_INVALID, std::string("unknown option or value out of range: ") + name + " = " +
                                             std::to_string((long long)value));
         // the workspace may be in use by a frame queued on any stream
@@ -776,14 +776,12 @@ int pt_renderer_get_option(const pt_renderer *r, const char *name, int64_t *valu
         *value = r->gpus[0].ds.nnodes;
         return PT_OK;
     }
-    if (tuning_get(r->gpus[0].ws.tune, name, value) != PT_OK) return fail(PT_ERR_INVALID, std::string("unknown option: ") + name);
+    if (!tuning_get(r->gpus[0].ws.tune, name, value)) return fail(PT_ERR_INVALID, std::string("unknown option: ") + name);
     return PT_OK;
 }
 
 const char *pt_option_name(int index) {
-    int n = 0;
-    while (TUNING_NAMES[n]) n++;
-    return index >= 0 && index < n ? TUNING_NAMES[index] : nullptr;
+    return index >= 0 && index < KNOB_COUNT ? KNOBS[index].name : nullptr;
 }
 
 int pt_renderer_peer_access(const pt_renderer *r, int *pairs, int *enabled) {

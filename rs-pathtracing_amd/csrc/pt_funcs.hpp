@@ -18,14 +18,14 @@
 #include <cmath>
 #include <cstdint>
 
+#include "pt_dims.hpp"  // FuncKind, F_ANY, F_NONE
+
 #ifndef PT_HD
 #define PT_HD __host__ __device__ __forceinline__
 #endif
 
 namespace pt {
 namespace march {
-
-enum FuncKind : int32_t { F_HEART = 0, F_SINE = 1, F_STAR = 2, F_DUPIN = 3, F_HUNTS = 4, F_CUSHION = 5 };
 
 // Per-shape constants of a function, precomputed on the host exactly as the
 // reference computes them inside shape_func (pure functions of the JSON
@@ -308,13 +308,7 @@ PT_HD bool shape_bound(const FParams &F, double ox, double oy, double oz, double
                           ox * ox + oy * oy + oz * oz - r * r, start, end);
 }
 
-// Compile-time function kind: FK >= 0 instantiates one function (a scene
-// whose marched shapes are all Hearts runs the Heart-only build: no dispatch,
-// no unused constants in registers); FK = F_ANY dispatches on F.func.
-constexpr int F_ANY = -1;
-// F_NONE: the scene has no ray-marched shape (the bounce build for large BVHs without one, C5): the helpers
-// below are never reached at run time and compile to nothing
-constexpr int F_NONE = -2;
+// The helpers by compile-time function kind (FuncKind, F_ANY, F_NONE: pt_dims.hpp).
 
 template <int FK>
 PT_HD double shape_f_k(const FParams &F, double x, double y, double z) {

@@ -14,8 +14,6 @@
 #include <cstdlib>
 #include <cstring>
 
-constexpr int DEFAULT_WAVES = 4;  // C5 (100k spheres, compact BVH): 2 waves 845-849, 3: 1044, 4: 1109 M samples/s
-
 namespace pt {
 
 using dev::Ray;
@@ -276,150 +274,53 @@ static dev::Scene dscene(const DeviceScene &s) {
     return d;
 }
 
-// Attenuation-stack width by depth: one 32-bit material id per bounce.  The widest build holds MAX_REG_DEPTH ids
-// (pt_kernel.hpp): every launcher below sends a deeper call elsewhere (the wavefront engine, the memory-stack probe)
-// or refuses it.
-static_assert(MAX_REG_DEPTH == 2 * 32, "IdStack<32> holds 64 ids");
-#define PT_DISPATCH_NW(depth, CALL)        \
-    do {                                   \
-        if ((depth) <= 8) {                \
-            constexpr int NW = 4;          \
-            CALL;                          \
-        } else if ((depth) <= 16) {        \
-            constexpr int NW = 8;          \
-            CALL;                          \
-        } else if ((depth) <= 32) {        \
-            constexpr int NW = 16;         \
-            CALL;                          \
-        } else {                           \
-            constexpr int NW = 32;         \
-            CALL;                          \
-        }                                  \
-    } while (0)
-
-// ------------------------------------------------------------- tuning
-const char *const TUNING_NAMES[] = {"engine", "mega_waves", "diag", "wf_slots", "wf_paths", "wf_min_chunks",
-                                    "wf_bounce_waves", "wf_march_slice", "wf_walk", "bvh_leaf", nullptr};
-
-static int64_t *tuning_field(Tuning *t, const char *name, int64_t *lo, int64_t *hi, int **iv) {
-    struct F {
-        const char *n;
-        int Tuning::*i;
-        int64_t lo, hi;
-    };
-    static const F fs[] = {
-        {"engine", &Tuning::engine, 0, 2},
-        {"mega_waves", &Tuning::mega_waves, 2, 5},
-        {"diag", &Tuning::diag, 0, 1},
-        {"wf_slots", &Tuning::wf_slots, 1, WaveWorkspace::MAX_SLOTS},
-        {"wf_min_chunks", &Tuning::wf_min_chunks, 1, 4096},
-        {"wf_bounce_waves", &Tuning::wf_bounce_waves, 2, 8},
-        {"wf_march_slice", &Tuning::wf_march_slice, 0, 1 << 20},
-        {"wf_walk", &Tuning::wf_walk, 0, 8},
-        {"bvh_leaf", &Tuning::bvh_leaf, 1, 16},
-    };
-    *iv = nullptr;
-    if (!name) return nullptr;
-    if (!strcmp(name, "wf_paths")) {  // (0 = by depth; 1..255 refused in tuning_set)
-        *lo = 0;
-        *hi = (int64_t)1 << 28;
-        return &t->wf_paths;
+// The probes' builds by attenuation-stack width (builds::stack_words, pt_builds.hpp): every launcher below sends a
+// call deeper than MAX_REG_DEPTH elsewhere (the memory-stack probe) or refuses it.
+#define PT_DISPATCH_NW(depth, CALL)                                        \
+    switch (builds::stack_words(depth)) {                                  \
+    case 4: { constexpr int NW = 4; CALL; } break;                         \
+    case 8: { constexpr int NW = 8; CALL; } break;                         \
+    case 16: { constexpr int NW = 16; CALL; } break;                       \
+    default: { constexpr int NW = 32; CALL; } break;                       \
     }
-    for (const F &f : fs)
-        if (!strcmp(name, f.n)) {
-            *lo = f.lo;
-            *hi = f.hi;
-            *iv = &(t->*(f.i));
-            return nullptr;
-        }
-    return nullptr;
-}
-
-int tuning_set(Tuning *t, const char *name, int64_t v) {
-    int64_t lo = 0, hi = 0;
-    int *iv = nullptr;
-    int64_t *lv = tuning_field(t, name, &lo, &hi, &iv);
-    if (!lv && !iv) return PT_ERR_INVALID;
-    if (v < lo || v > hi) return PT_ERR_INVALID;
-    if (!strcmp(name, "wf_bounce_waves") && !(v == 2 || v == 3 || v == 4 || v == 5 || v == 6 || v == 8))
-        return PT_ERR_INVALID;
-    if (!strcmp(name, "wf_walk") && !(v == 0 || v == 4 || v == 5 || v == 6 || v == 8)) return PT_ERR_INVALID;
-    if (!strcmp(name, "wf_paths") && v > 0 && v < 256) return PT_ERR_INVALID;
-    if (lv) *lv = v;
-    else *iv = (int)v;
-    return PT_OK;
-}
-
-int tuning_get(const Tuning &t0, const char *name, int64_t *v) {
-    Tuning t = t0;
-    int64_t lo = 0, hi = 0;
-    int *iv = nullptr;
-    int64_t *lv = tuning_field(&t, name, &lo, &hi, &iv);
-    if (!lv && !iv) return PT_ERR_INVALID;
-    *v = lv ? *lv : (int64_t)*iv;
-    return PT_OK;
-}
-
-Tuning tuning_defaults() { return Tuning{}; }
 
 hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P, double *out, hipStream_t st,
-                              WaveWorkspace *ws, int fkind);
+                              WaveWorkspace *ws, const builds::Choice &ch);
 
-// Frames of at least this many samples take the wavefront engine even
-// without ray-marched shapes: on C5 (100k spheres, BVH) it runs 1394 against
-// the megakernel's 1026 M samples/s (the path state is dense by position and
-// the bounce waves stay full where the megakernel's lanes idle on finished
-// paths and unequal BVH walks); below it the per-chunk launches cost more
-// than they save.
-constexpr uint64_t WAVE_MIN_SAMPLES = 1ull << 22;
-
-static bool use_wavefront(const DeviceScene &s, const FrameParams &P, WaveWorkspace *ws) {
-    if (s.ext) return true;  // textures / Torus: the extended builds live in the wavefront engine
-    const int engine = ws ? ws->tune.engine : 1;
-    if (engine == 1) return false;
-    if (engine == 2) return ws != nullptr;
-    const uint64_t samples = (uint64_t)P.tile_count * TILE * TILE * P.spp;
-    return ws != nullptr && (s.diag & 1) == 0 && (s.nmarch > 0 || samples >= WAVE_MIN_SAMPLES);
-}
-
-hipError_t launch_render(const DeviceScene &s, const FrameParams &P, double *out, hipStream_t st,
-                         WaveWorkspace *ws) {
+hipError_t launch_render(const DeviceScene &s, const FrameParams &P, double *out, hipStream_t st, WaveWorkspace &ws) {
     if (P.tile_count == 0) return hipSuccess;
-    if (ws) ws->refusal[0] = 0;
-    if (P.depth > MAX_REG_DEPTH) {
-        // a deep frame: the wavefront engine's id stacks live in memory; whatever `engine` says and however small the
-        // frame, and never the megakernel
-        const bool window = P.s_begin > 0 || (P.s_end && P.s_end < P.spp);
-        if (!ws || (window && P.s_begin >= (P.s_end ? P.s_end : P.spp))) return hipErrorInvalidValue;
-        return launch_render_wave(dscene(s), P, out, st, ws, s.fkind);
-    }
-    if (P.s_begin > 0 || (P.s_end && P.s_end < P.spp)) {
-        // a sample window: only the wavefront engine keeps running sums across launches
-        if (!ws || P.s_begin >= (P.s_end ? P.s_end : P.spp)) return hipErrorInvalidValue;
-        return launch_render_wave(dscene(s), P, out, st, ws, s.fkind);
-    }
-    if (use_wavefront(s, P, ws)) return launch_render_wave(dscene(s), P, out, st, ws, s.fkind);
-    KernelTimer *tm = ws ? ws->timer : nullptr;
-    hipError_t e0 = timer_begin(tm, st, K_MEGA);
+    ws.refusal[0] = 0;
+    builds::Inputs in{};
+    in.ext = s.ext != 0;
+    in.fkind = s.fkind;
+    in.nnodes = s.nnodes;
+    in.nmarch = s.nmarch;
+    in.has_qnodes = s.qnodes != nullptr;
+    in.scene_diag = s.diag;
+    in.depth = P.depth;
+    in.samples = (uint64_t)P.tile_count * TILE * TILE * P.spp;
+    in.window = P.s_begin > 0 || (P.s_end && P.s_end < P.spp);
+    in.window_empty = P.s_begin >= (P.s_end ? P.s_end : P.spp);
+    in.wave_diag_on = PT_WAVE_DIAG && ws.diag;
+    in.diag_buffer = ws.diag != nullptr;
+    in.tune = ws.tune;
+    const builds::Choice ch = builds::choose(in);
+    if (ch.engine == builds::REFUSE) return hipErrorInvalidValue;
+    if (ch.engine == builds::WAVE) return launch_render_wave(dscene(s), P, out, st, &ws, ch);
+    hipError_t e0 = timer_begin(ws.timer, st, K_MEGA);
     if (e0 != hipSuccess) return e0;
-    if (P.depth <= 8 && s.fkind == march::F_HEART) {
-        // Heart-only (or no marched shape): the single-function build
-        // megakernel register budget (Tuning::mega_waves); depths > 8 use the
-        // 2-wave build: their attenuation stacks are wider
-        switch (ws ? ws->tune.mega_waves : DEFAULT_WAVES) {
-        case 2: render_tiles<4, 2, march::F_HEART><<<P.tile_count, 256, 0, st>>>(dscene(s), P, out); break;
-        case 3: render_tiles<4, 3, march::F_HEART><<<P.tile_count, 256, 0, st>>>(dscene(s), P, out); break;
-        case 5: render_tiles<4, 5, march::F_HEART><<<P.tile_count, 256, 0, st>>>(dscene(s), P, out); break;
-        default: render_tiles<4, 4, march::F_HEART><<<P.tile_count, 256, 0, st>>>(dscene(s), P, out); break;
-        }
-    } else if (P.depth <= 8) {
-        render_tiles<4, 2><<<P.tile_count, 256, 0, st>>>(dscene(s), P, out);
-    } else {
-        PT_DISPATCH_NW(P.depth, (render_tiles<NW, 2><<<P.tile_count, 256, 0, st>>>(dscene(s), P, out)));
+    bool launched = false;
+#define X(NW, WAVES, FK)                                                             \
+    if (ch.mega.is(NW, WAVES, FK)) {                                                 \
+        render_tiles<NW, WAVES, FK><<<P.tile_count, 256, 0, st>>>(dscene(s), P, out); \
+        launched = true;                                                             \
     }
+    PT_MEGA_BUILDS(X)
+#undef X
+    if (!launched) return hipErrorInvalidValue;  // (no frame: tests/test_builds.py)
     e0 = hipGetLastError();
     if (e0 != hipSuccess) return e0;
-    return timer_end(tm, st);
+    return timer_end(ws.timer, st);
 }
 
 hipError_t launch_unshard(const double *g, uint32_t width, uint32_t height, uint32_t world, double *frame,

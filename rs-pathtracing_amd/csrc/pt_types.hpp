@@ -5,7 +5,7 @@
 #pragma once
 #include <cstdint>
 
-#include "pt_dims.hpp"  // TILE
+#include "pt_dims.hpp"  // TILE, BIG_BVH_NODES
 
 namespace pt {
 
@@ -106,8 +106,6 @@ struct alignas(64) DQGrid {
     float pad[3];
 };
 static_assert(sizeof(DQGrid) == 64, "DQGrid is one cache line");
-
-constexpr int BIG_BVH_NODES = 1 << 15;  // binary nodes from which the bounce runs its large-tree builds (C5)
 
 // A one-shape leaf of the large-tree walk's quantized nodes (round 6): the shape id, and for a sphere whose inverse
 // transform is a diagonal scale plus a translation (DShape::axis) the six entries sphere_axis_t reads (m0, m5,

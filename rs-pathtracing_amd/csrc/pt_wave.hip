@@ -1027,7 +1027,6 @@ __global__ __launch_bounds__(256, WAVES) void wf_walk(const WfArgs *__restrict__
 // (dev::unwind; end_path left the leaf and the stack depth).  Sample by
 // sample: a version unwinding 8 samples level by level together needs more
 // registers and measured slower (the kernel is latency-bound: occupancy wins).
-constexpr uint32_t UNWIND_PIXELS = 1u << 18;  // chunks of fewer pixels unwind in their own pass (wf_unwind)
 // The unwind of every slot of the chunk, one thread per slot, in place (the leaf record's radiance becomes the
 // sample's): a thread per pixel unwinding its samples one after another waits for two dependent loads per sample.
 template <bool EXT>
@@ -1259,117 +1258,66 @@ static uint32_t march_grid() {
     return blocks;
 }
 
-// The scenes whose BVH walk runs in wf_walk (Tuning::wf_walk): a large tree (BIG_BVH_NODES, pt_types.hpp: C5's
-// 100k-sphere tree has ~200k nodes, cornell's ~960) and no marched shape.
-static bool walk_split(const dev::Scene &sc, const Tuning &tu) {
-    return tu.wf_walk && !sc.ext && sc.nnodes >= BIG_BVH_NODES && sc.nmarch == 0;
-}
+// The launchers look the build that builds::choose picked (pt_builds.hpp) up in the list of the instantiated ones;
+// no frame falls off a list's end (tests/test_builds.py).
 
+// The bounce of iteration it: the chunk's camera rays (FIRST), or the live list of it.
 template <bool FIRST>
-static void launch_bounce_build(uint32_t blocks, hipStream_t st, const dev::Scene &sc, const WfArgs *A, int it,
-                          unsigned long long *diag, int fkind, int waves, bool split, bool deep) {
-    if (deep) {  // depth > 64: the generic builds with the stack count in the id stack, whatever the scene
-        if (sc.ext)
-            wf_bounce<FIRST, 2, march::F_ANY, true, false, false, true><<<blocks, 256, 0, st>>>(A, it);
-        else
-            wf_bounce<FIRST, 2, march::F_ANY, false, false, false, true><<<blocks, 256, 0, st>>>(A, it);
-        return;
+static hipError_t run_bounce(const builds::Bounce &b, uint32_t blocks, hipStream_t st, const WfArgs *A, int it,
+                             unsigned long long *diag) {
+#define X(WAVES, FK, EXT, BIGBVH, SPLIT, DEEP)                                                       \
+    if (b.is(WAVES, FK, EXT, BIGBVH, SPLIT, DEEP)) {                                                 \
+        wf_bounce<FIRST, WAVES, FK, EXT, BIGBVH, SPLIT, DEEP><<<blocks, 256, 0, st>>>(A, it, diag); \
+        return hipSuccess;                                                                           \
     }
-    if (split) {  // shade and store the new ray only: wf_walk traces it
-        switch (waves) {
-        case 4: wf_bounce<FIRST, 4, march::F_NONE, false, true, true><<<blocks, 256, 0, st>>>(A, it); break;
-        case 5: wf_bounce<FIRST, 5, march::F_NONE, false, true, true><<<blocks, 256, 0, st>>>(A, it); break;
-        default: wf_bounce<FIRST, 3, march::F_NONE, false, true, true><<<blocks, 256, 0, st>>>(A, it); break;
-        }
-        return;
-    }
-    if (sc.ext) {  // non-solid textures or a Torus: the generic extended build
-        wf_bounce<FIRST, 2, march::F_ANY, true><<<blocks, 256, 0, st>>>(A, it);
-        return;
-    }
-    if (fkind != march::F_HEART) {  // another ray-marched function: the generic build
-        wf_bounce<FIRST, 2, march::F_ANY><<<blocks, 256, 0, st>>>(A, it);
-        return;
-    }
-    if (PT_WAVE_DIAG && diag) {  // (diagnostics builds)
-        wf_bounce<FIRST, 2, march::F_HEART><<<blocks, 256, 0, st>>>(A, it, diag);
-        return;
-    }
-    if (sc.nnodes >= BIG_BVH_NODES && sc.nmarch == 0) {  // a large BVH and no marched shape (C5): the FMA slab
-        switch (waves) {                                   // build without march pre-check or Heart code
-        case 4: wf_bounce<FIRST, 4, march::F_NONE, false, true><<<blocks, 256, 0, st>>>(A, it); break;
-        case 5: wf_bounce<FIRST, 5, march::F_NONE, false, true><<<blocks, 256, 0, st>>>(A, it); break;
-        default: wf_bounce<FIRST, 3, march::F_NONE, false, true><<<blocks, 256, 0, st>>>(A, it); break;
-        }
-        return;
-    }
-    if (waves == 3 && sc.nnodes >= BIG_BVH_NODES) {  // the default budget, a large BVH with a marched shape
-        wf_bounce<FIRST, 3, march::F_HEART, false, true><<<blocks, 256, 0, st>>>(A, it);
-        return;
-    }
-    switch (waves) {  // Tuning::wf_bounce_waves
-    case 2: wf_bounce<FIRST, 2, march::F_HEART><<<blocks, 256, 0, st>>>(A, it); break;
-    case 4: wf_bounce<FIRST, 4, march::F_HEART><<<blocks, 256, 0, st>>>(A, it); break;
-    case 5: wf_bounce<FIRST, 5, march::F_HEART><<<blocks, 256, 0, st>>>(A, it); break;
-    case 6: wf_bounce<FIRST, 6, march::F_HEART><<<blocks, 256, 0, st>>>(A, it); break;
-    case 8: wf_bounce<FIRST, 8, march::F_HEART><<<blocks, 256, 0, st>>>(A, it); break;
-    default: wf_bounce<FIRST, 3, march::F_HEART><<<blocks, 256, 0, st>>>(A, it); break;
-    }
+    PT_BOUNCE_BUILDS(X)
+#undef X
+    return hipErrorInvalidValue;
 }
 
-// The bounce of iteration it: the chunk's camera rays (first), or the live list of it.
-static void launch_bounce(bool first, uint32_t blocks, hipStream_t st, const dev::Scene &sc, const WfArgs *A, int it,
-                          unsigned long long *diag, int fkind, int waves, bool split, bool deep) {
-    if (first)
-        launch_bounce_build<true>(blocks, st, sc, A, it, diag, fkind, waves, split, deep);
-    else
-        launch_bounce_build<false>(blocks, st, sc, A, it, diag, fkind, waves, split, deep);
-}
-
-// The new rays' BVH walk, over the live list of it + 1 (walk_split scenes).
-static void launch_walk(uint32_t blocks, hipStream_t st, const dev::Scene &sc, const WfArgs *A, int it, int waves) {
-    if (!sc.qnodes) {  // (a tree without the quantized form)
-        wf_walk<5, false><<<blocks, 256, 0, st>>>(A, it);
-        return;
+// The new rays' BVH walk, over the live list of it + 1 (builds::Walk::on).
+static hipError_t run_walk(const builds::Walk &w, uint32_t blocks, hipStream_t st, const WfArgs *A, int it) {
+#define X(WAVES, QN)                                      \
+    if (w.is(WAVES, QN)) {                                \
+        wf_walk<WAVES, QN><<<blocks, 256, 0, st>>>(A, it); \
+        return hipSuccess;                                \
     }
-    switch (waves) {  // the walk's register budget, waves per SIMD (Tuning::wf_walk)
-    case 4: wf_walk<4, true><<<blocks, 256, 0, st>>>(A, it); break;
-    case 6: wf_walk<6, true><<<blocks, 256, 0, st>>>(A, it); break;
-    case 8: wf_walk<8, true><<<blocks, 256, 0, st>>>(A, it); break;
-    default: wf_walk<5, true><<<blocks, 256, 0, st>>>(A, it); break;
-    }
+    PT_WALK_BUILDS(X)
+#undef X
+    return hipErrorInvalidValue;
 }
 
 // The march queue of iteration it, on the persistent grid.
-static void launch_march(hipStream_t st, const WfArgs *A, int it, unsigned long long *diag, int fkind,
-                         uint32_t slice) {
+static hipError_t run_march(const builds::March &m, hipStream_t st, const WfArgs *A, int it,
+                            unsigned long long *diag, uint32_t slice) {
     const uint32_t blocks = march_grid();
-    if (fkind != march::F_HEART)  // another ray-marched function: the generic build
-        wf_march<march::F_ANY><<<blocks, 256, 0, st>>>(A, it, nullptr, slice);
-    else
-        wf_march<march::F_HEART><<<blocks, 256, 0, st>>>(A, it, diag, slice);
+#define X(FK)                                                        \
+    if (m.is(FK)) {                                                  \
+        wf_march<FK><<<blocks, 256, 0, st>>>(A, it, diag, slice); \
+        return hipSuccess;                                           \
+    }
+    PT_MARCH_BUILDS(X)
+#undef X
+    return hipErrorInvalidValue;
 }
 
 // One thread per slot of a chunk of few pixels (UNWIND_PIXELS).
-static void launch_unwind(uint32_t slots, hipStream_t st, const dev::Scene &sc, const WfArgs *A) {
-    if (sc.ext)
-        wf_unwind<true><<<(slots + 255) / 256, 256, 0, st>>>(A);
-    else
-        wf_unwind<false><<<(slots + 255) / 256, 256, 0, st>>>(A);
+template <bool EXT>
+static hipError_t run_unwind(uint32_t slots, hipStream_t st, const WfArgs *A) {
+    wf_unwind<EXT><<<(slots + 255) / 256, 256, 0, st>>>(A);
+    return hipSuccess;
 }
 
 // One thread per pixel; unwound: wf_unwind has run over the chunk's slots.
-static void launch_reduce(uint32_t npix, hipStream_t st, const dev::Scene &sc, const WfArgs *A, bool unwound,
-                          int first, int last, double *out) {
+template <bool EXT>
+static hipError_t run_reduce(uint32_t npix, hipStream_t st, const WfArgs *A, bool unwound, int first, int last,
+                             double *out) {
     const uint32_t blocks = (npix + 255) / 256;
-    if (sc.ext && unwound)
-        wf_reduce<true, true><<<blocks, 256, 0, st>>>(A, first, last, out);
-    else if (sc.ext)
-        wf_reduce<true, false><<<blocks, 256, 0, st>>>(A, first, last, out);
-    else if (unwound)
-        wf_reduce<false, true><<<blocks, 256, 0, st>>>(A, first, last, out);
+    if (unwound)
+        wf_reduce<EXT, true><<<blocks, 256, 0, st>>>(A, first, last, out);
     else
-        wf_reduce<false, false><<<blocks, 256, 0, st>>>(A, first, last, out);
+        wf_reduce<EXT, false><<<blocks, 256, 0, st>>>(A, first, last, out);
+    return hipSuccess;
 }
 
 // One timed launch (or group of launches under one record) on a chunk's stream: the timer's events around it when
@@ -1378,7 +1326,7 @@ template <class F>
 static hipError_t timed(KernelTimer *t, hipStream_t st, int kind, F launch) {
     hipError_t e = timer_begin(t, st, kind);
     if (e != hipSuccess) return e;
-    launch();
+    if ((e = launch()) != hipSuccess) return e;
     if ((e = hipGetLastError()) != hipSuccess) return e;
     return timer_end(t, st);
 }
@@ -1419,9 +1367,10 @@ struct Slot {
 static hipStream_t slot_stream(const WaveWorkspace *ws, hipStream_t st, int j) { return j == 0 ? st : ws->side[j - 1]; }
 
 // Queues this rank's tiles of the frame (of a resumable frame: the window [s_begin, s_end) of its samples) on st:
-// the plan (pt_plan.hpp), the workspace, the chunks' argument blocks, then the chunks step by step.
+// the plan (pt_plan.hpp), the workspace, the chunks' argument blocks, then the chunks step by step, with the kernel
+// builds of `bc` (builds::choose, pt_builds.hpp).
 hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, double *out, hipStream_t st,
-                              WaveWorkspace *ws, int fkind) {
+                              WaveWorkspace *ws, const builds::Choice &bc) {
     if (P0.tile_count == 0 || P0.spp == 0) return hipSuccess;
     const Tuning &tu = ws->tune;
     plan::Input in;
@@ -1432,9 +1381,7 @@ hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
     in.depth = P0.depth;
     in.progressive = P0.stop != nullptr;
     in.textured = sc.tex != nullptr;
-    // pre-selected march jobs (one marched shape): the bounce kernel hands the march its object-space ray
-    // and bound (C2 +9 %: iso march 340 -> 275 ms, bounce 248 -> 256, round 1)
-    in.presel = sc.nmarch == 1 && !ws->diag;
+    in.presel = bc.presel;
     in.wf_paths = tu.wf_paths;
     in.wf_slots = tu.wf_slots;
     in.wf_min_chunks = tu.wf_min_chunks;
@@ -1498,10 +1445,8 @@ hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
     }
 
     const uint32_t march_slice = (uint32_t)tu.wf_march_slice;
-    // a deep frame (depth > 64) runs the generic DEEP bounce builds: no wf_walk route, no Heart-only march
-    const bool deep = plan::deep(P0.depth);
-    const bool split = !deep && walk_split(sc, tu);
-    if (deep) fkind = -1;
+    unsigned long long *const bounce_diag = bc.bounce.diag ? ws->diag : nullptr;
+    unsigned long long *const march_diag = bc.march.diag ? ws->diag : nullptr;
     // The launches' argument blocks (WfArgs): chunk ci at iteration parity h is block 2 ci + h.  They are
     // written to the pinned staging buffer, which the previous frame's copy must have read, and copied to the
     // device on st after the previous frame's kernels (the wait on ws->done above), before the side streams fork.
@@ -1560,8 +1505,8 @@ hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
                 if (bb > WF_BOUNCE_CAP) bb = WF_BOUNCE_CAP;
                 // iteration 0: slots [0, paths) are the chunk's camera rays
                 e = timed(ws->timer, cs, K_BOUNCE, [&] {
-                    launch_bounce(it == 0, it == 0 ? (paths + 255) / 256 : bb, cs, sc, A, it, ws->diag, fkind,
-                                  tu.wf_bounce_waves, split, deep);
+                    return it == 0 ? run_bounce<true>(bc.bounce, (paths + 255) / 256, cs, A, it, bounce_diag)
+                                   : run_bounce<false>(bc.bounce, bb, cs, A, it, bounce_diag);
                 });
                 if (e != hipSuccess) return e;
                 if (it == iters - 1) continue;  // the last bounce only shades
@@ -1577,14 +1522,16 @@ hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
                     cp_scatter<<<cgrid, CP_BLOCK, 0, cs>>>(v.status, cp_blk, CL, &v.cnt[it * 4 + 2], v.list, v.mq,
                                                            n_in, paths);
                     if (P0.stop) stop_gate<<<1, 64, 0, cs>>>(P0.stop, v.cnt, it);
+                    return hipSuccess;
                 });
                 if (e != hipSuccess) return e;
-                if (split) {
-                    e = timed(ws->timer, cs, K_WALK, [&] { launch_walk(bb, cs, sc, A, it, tu.wf_walk); });
+                if (bc.walk.on) {
+                    e = timed(ws->timer, cs, K_WALK, [&] { return run_walk(bc.walk, bb, cs, A, it); });
                     if (e != hipSuccess) return e;
                 }
-                if (sc.nmarch == 0) continue;  // no ray-marched shape: the march queue is always empty
-                e = timed(ws->timer, cs, K_MARCH, [&] { launch_march(cs, A, it, ws->diag, fkind, march_slice); });
+                if (!bc.march.on) continue;  // no ray-marched shape: the march queue is always empty
+                e = timed(ws->timer, cs, K_MARCH,
+                          [&] { return run_march(bc.march, cs, A, it, march_diag, march_slice); });
                 if (e != hipSuccess) return e;
             }
         }
@@ -1599,16 +1546,21 @@ hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
             // chunk's sums.  Larger chunks fill the machine with pixels, and the extra pass over the slots costs
             // more than it saves: C1 +1.5 %, but C2 -2.2 to -3.5 %, C5 -2.7 %, even C2 depth 50 -1.4 %
             // (profiles/r6/ab/r6m_reduce_split_summary.txt, r6q_unwind_all_summary.txt)
-            const bool unwound = npix < UNWIND_PIXELS;
+            const bool unwound = npix < builds::UNWIND_PIXELS;
             if (unwound) {
-                e = timed(ws->timer, cs, K_UNWIND, [&] { launch_unwind(ch.ns * npix, cs, sc, A); });
+                e = timed(ws->timer, cs, K_UNWIND, [&] {
+                    return bc.ext ? run_unwind<true>(ch.ns * npix, cs, A) : run_unwind<false>(ch.ns * npix, cs, A);
+                });
                 if (e != hipSuccess) return e;
             }
             if (slots > 1 && c > 0 && (e = hipStreamWaitEvent(cs, ws->reduced, 0)) != hipSuccess) return e;
             // first: 1 = sums from zero, 2 = from out's running sums; last: 1 = means, 2 = running sums to out
             const int first = ch.s0 == s_begin ? (s_begin == 0 ? 1 : 2) : 0;
             const int last = ch.s0 + ch.ns >= s_end ? (s_end == P0.spp ? 1 : 2) : 0;
-            e = timed(ws->timer, cs, K_REDUCE, [&] { launch_reduce(npix, cs, sc, A, unwound, first, last, out); });
+            e = timed(ws->timer, cs, K_REDUCE, [&] {
+                return bc.ext ? run_reduce<true>(npix, cs, A, unwound, first, last, out)
+                              : run_reduce<false>(npix, cs, A, unwound, first, last, out);
+            });
             if (e != hipSuccess) return e;
             if (slots > 1 && (e = hipEventRecord(ws->reduced, cs)) != hipSuccess) return e;
         }

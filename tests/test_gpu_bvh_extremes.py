@@ -73,3 +73,49 @@ def test_walk_register_budgets(pt, waves):
     img, ref = render_both(pt, make_scenes.synthetic(40000), w=96, h=54, wf_walk=waves)
     bad = np.flatnonzero(np.any(img != ref, axis=1))
     assert len(bad) == 0, "%d of %d pixels differ" % (len(bad), len(img))
+
+
+# The large-tree bounce builds that the default wf_bounce_waves does not reach (the bounce table of DESIGN.md §2,
+# rows 6 to 8).  Frames of 96x54, 2 spp, depth 8; every pixel equals the oracle's.
+PLAIN_REF = {}
+
+
+@pytest.mark.parametrize("waves", [4, 6])
+def test_large_tree_bounce_budgets_without_walk(pt, waves):
+    """Row 6: the walk inside the bounce (wf_walk 0), no marched shape: the F_NONE large-tree builds.  There are
+    3-, 4- and 5-wave ones, so wf_bounce_waves 4 runs its own build and 6 runs the 3-wave build."""
+    import make_scenes
+    img, ref = render_both(pt, make_scenes.synthetic(40000), w=96, h=54, wf_walk=0, wf_bounce_waves=waves)
+    PLAIN_REF.setdefault("ref", ref)
+    bad = np.flatnonzero(np.any(img != ref, axis=1))
+    assert len(bad) == 0, "%d of %d pixels differ" % (len(bad), len(img))
+
+
+def with_heart(doc):
+    """doc plus the Heart of make_scenes.marched() and its Copper material, above the grid at the camera's look-at
+    point (the origin)."""
+    import make_scenes
+    doc = json.loads(json.dumps(doc))
+    src = make_scenes.marched()
+    heart = json.loads(json.dumps(next(s for s in src["shapes"] if s.get("name") == "Heart")))
+    heart["transform"]["translate"] = [0.0, 1.2, 0.0]
+    doc["shapes"].append(heart)
+    doc["materials"]["Copper"] = src["materials"]["Copper"]
+    return doc
+
+
+@pytest.mark.parametrize("waves", [3, 4])
+def test_large_tree_bounce_with_a_heart(pt, waves):
+    """Rows 7 and 8: a large tree with a marched shape.  wf_bounce_waves 3 runs the large-tree Heart build, 4 the
+    small-tree 4-wave Heart build (there is no large-tree one at that budget).  The oracle's BVH holds the Heart
+    (its leaves are shapes of any kind), so the reference is its BVH traversal as everywhere in this file; its
+    frame differs from the one without the Heart, so paths did reach the march."""
+    import make_scenes
+    plain = make_scenes.synthetic(40000)
+    img, ref = render_both(pt, with_heart(plain), w=96, h=54, wf_bounce_waves=waves)
+    bad = np.flatnonzero(np.any(img != ref, axis=1))
+    assert len(bad) == 0, "%d of %d pixels differ" % (len(bad), len(img))
+    if "ref" not in PLAIN_REF:
+        PLAIN_REF["ref"] = O.Scene(json.dumps(plain), seed=1).use_bvh(True, 7).render(96, 54, 2, 8, 3,
+                                                                                     threads=host_threads())
+    assert np.any(ref != PLAIN_REF["ref"]), "the Heart is not in the frame"
