@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <stdexcept>
 
 namespace pt {
@@ -301,6 +302,17 @@ void build_qnodes(Accel &a, const Scene &sc) {
     a.qleaves.swap(recs);
     a.qbound = (float)bound;
     if ((double)a.qbound < bound) a.qbound = std::nextafter(a.qbound, INFINITY);
+}
+
+std::vector<DQGrid> pack_qnodes(const Accel &a) {
+    if (a.qnodes.empty()) return {};
+    const size_t ro = qleaf_offset(a.nodes_per_octant()), rb = a.qleaves.size() * sizeof(DLeafRec);
+    std::vector<DQGrid> buf((ro + rb) / sizeof(DQGrid));  // zeroed: the padding node and the gap before the records
+    for (int k = 0; k < 3; k++) buf[0].g0[k] = a.qg0[k], buf[0].gs[k] = a.qgs[k];
+    buf[0].bound = a.qbound;
+    std::memcpy(&buf[1], a.qnodes.data(), a.qnodes.size() * sizeof(DNodeQ));
+    if (rb) std::memcpy((char *)buf.data() + ro, a.qleaves.data(), rb);
+    return buf;
 }
 
 Accel build_accel(const Scene &sc, int json_shapes, int leaf_max) {

@@ -13,6 +13,7 @@
 //   * `march` — ray-marched shapes, tested last behind their padded box
 //               against the best distance so far.
 #pragma once
+#include <array>
 #include <cstdint>
 #include <vector>
 
@@ -53,6 +54,68 @@ Accel build_accel(const Scene &sc, int json_shapes, int leaf_max = 1);
 // the quantized nodes of a's layouts (build_accel does this for trees of at least BIG_BVH_NODES nodes per layout;
 // tests call it for smaller ones)
 void build_qnodes(Accel &a, const Scene &sc);
+
+// The quantized nodes' buffer as wf_walk reads it, whole: the grid at byte 0, the eight layouts from byte 64, one
+// zeroed DNodeQ after the last layout (the walk reads one node past it), zeros up to qleaf_offset(nodes_per_octant())
+// and the one-shape leaves' records from there.  Empty for a tree without quantized nodes.
+std::vector<DQGrid> pack_qnodes(const Accel &a);
+static_assert(sizeof(DLeafRec) % sizeof(DQGrid) == 0, "pack_qnodes sizes its buffer in DQGrid units");
+
+// The kernels' view (dev::Scene, pt_types.hpp) is filled here and nowhere else, in two parts, from whatever buffers
+// the caller holds (device memory in the library, host vectors in the tests' and tools' host builds); the counts and
+// bounds come from the Scene / Accel.  `diag` and `guard` belong to the renderer.  A field added to dev::Scene
+// must be set by one of the two:
+static_assert(sizeof(dev::Scene) == 136, "a new dev::Scene field must be set by view_set_scene or view_set_accel");
+// the scene part; tex .. pixels are null for a scene without non-solid textures
+inline void view_set_scene(dev::Scene &v, const Scene &sc, const DShape *shapes, const DMaterial *mats,
+                           const DTexture *tex, const DPerlin *perlin, const DImage *images, const uint8_t *pixels) {
+    v.shapes = shapes;
+    v.mats = mats;
+    v.tex = tex;
+    v.perlin = perlin;
+    v.images = images;
+    v.pixels = pixels;
+    v.nmats = (int)sc.materials.size();
+    v.ext = scene_builds(sc).ext;
+}
+// the acceleration part; qnodes is the pack_qnodes buffer (null without one)
+inline void view_set_accel(dev::Scene &v, const DNodeC *nodes, const DQGrid *qnodes, const int32_t *leaf,
+                           const int32_t *lin, const int32_t *march, const DBox *boxes, int nnodes, int nlin,
+                           int nmarch, float bvh_bound) {
+    v.nodes = nodes;
+    v.qnodes = qnodes;
+    v.leaf = leaf;
+    v.lin = lin;
+    v.march = march;
+    v.boxes = boxes;
+    v.nnodes = nnodes;  // per octant layout
+    v.nlin = nlin;
+    v.nmarch = nmarch;
+    v.bvh_bound = bvh_bound;
+}
+inline void view_set_accel(dev::Scene &v, const Accel &a, const DNodeC *nodes, const DQGrid *qnodes,
+                           const int32_t *leaf, const int32_t *lin, const int32_t *march, const DBox *boxes) {
+    view_set_accel(v, nodes, qnodes, leaf, lin, march, boxes, a.nodes_per_octant(), (int)a.lin.size(),
+                   (int)a.march.size(), a.bvh_bound);
+}
+// ... of another view (a staged structure's, when it is committed)
+inline void view_set_accel(dev::Scene &v, const dev::Scene &a) {
+    view_set_accel(v, a.nodes, a.qnodes, a.leaf, a.lin, a.march, a.boxes, a.nnodes, a.nlin, a.nmarch, a.bvh_bound);
+}
+// The buffers a view's owner frees: the acceleration part's first.
+constexpr size_t VIEW_ACCEL_BUFS = 6;
+inline std::array<const void *, 13> view_buffers(const dev::Scene &v) {
+    return {v.nodes, v.qnodes, v.leaf,   v.lin,    v.march,  v.boxes, v.shapes,
+            v.mats,  v.tex,    v.perlin, v.images, v.pixels, v.guard};
+}
+// A view over host vectors: what a host build of the device functions runs on.  qbuf: pack_qnodes(a), kept by the
+// caller.  A pointer is null exactly when its vector is empty.
+inline void view_of_host(dev::Scene &v, const Scene &sc, const Accel &a, const std::vector<DShape> &shapes,
+                         const std::vector<DMaterial> &mats, const std::vector<DQGrid> &qbuf) {
+    auto ptr = [](const auto &vec) { return vec.empty() ? nullptr : vec.data(); };
+    view_set_scene(v, sc, ptr(shapes), ptr(mats), ptr(sc.textures), ptr(sc.perlins), ptr(sc.images), ptr(sc.pixels));
+    view_set_accel(v, a, ptr(a.cnodes), ptr(qbuf), ptr(a.leaf), ptr(a.lin), ptr(a.march), ptr(a.boxes));
+}
 
 // conservative world AABB of one shape (reference get_bounding_box + padding)
 DBox shape_box(const HostShape &s);

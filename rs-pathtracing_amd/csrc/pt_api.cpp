@@ -303,15 +303,17 @@ int pt_camera_new(const double position[3], const double direction[3], const dou
 
 namespace {
 
+void free_buffers(const dev::Scene &v, size_t count) {
+    const auto bufs = view_buffers(v);
+    for (size_t k = 0; k < count; k++)
+        if (bufs[k]) (void)hipFree(const_cast<void *>(bufs[k]));
+}
+
 void free_share(GpuShare &g) {
     (void)hipSetDevice(g.device);
     if (g.stream) (void)hipStreamSynchronize(g.stream);
-    DeviceScene &d = g.ds;
-    void *bufs[] = {d.shapes, d.mats, d.nodes, d.qnodes, d.leaf, d.lin, d.march, d.boxes, d.tex, d.perlin,
-                    d.images, d.pixels, d.guard};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    d = DeviceScene{};
+    free_buffers(g.ds.view, view_buffers(g.ds.view).size());
+    g.ds = DeviceScene{};
     if (g.d_shard) (void)hipFree(g.d_shard);
     g.d_shard = nullptr;
     g.shard_cap = 0;
@@ -327,68 +329,47 @@ void free_share(GpuShare &g) {
 // structure is first staged in buffers of its own (stage_accel); only when
 // every device has staged it are the old buffers swapped out and freed
 // (commit_accel), so a failed upload leaves every device on its old, complete
-// structure.
-struct StagedAccel {
-    DNodeC *nodes = nullptr;
-    DQGrid *qnodes = nullptr;
-    int32_t *leaf = nullptr, *lin = nullptr, *march = nullptr;
-    DBox *boxes = nullptr;
-    int nnodes = 0, nlin = 0, nmarch = 0;
-    float bvh_bound = 0.f;
-};
+// structure.  A staged structure is a view with only its acceleration part set.
+using StagedAccel = dev::Scene;
 
+void free_staged(int device, StagedAccel &a) {
+    (void)hipSetDevice(device);
+    free_buffers(a, VIEW_ACCEL_BUFS);
+    a = StagedAccel{};
+}
+
+// A host vector in a device buffer of its own (one element's room for an empty vector), unless an earlier step
+// failed (err): the buffer, also when the copy into it failed, for the caller to free.
 // Test hook (renderer option "fault_accel_alloc" = n, kept per renderer): the
 // n-th device allocation of that renderer's next BVH rebuild fails as if the
 // device were out of memory.  `fault` is the renderer's counter (null when
 // creating a renderer: no hook).
-
-void free_staged(int device, StagedAccel &a) {
-    (void)hipSetDevice(device);
-    void *bufs[] = {a.nodes, a.qnodes, a.leaf, a.lin, a.march, a.boxes};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    a = StagedAccel{};
+template <class T>
+const T *upload(hipError_t &err, const std::vector<T> &vec, int *fault = nullptr) {
+    T *d = nullptr;
+    if (err == hipSuccess && fault && *fault > 0 && (*fault)-- == 1) err = hipErrorOutOfMemory;
+    if (err == hipSuccess) err = hipMalloc((void **)&d, (vec.empty() ? 1 : vec.size()) * sizeof(T));
+    if (err == hipSuccess && !vec.empty())
+        err = hipMemcpy(d, vec.data(), vec.size() * sizeof(T), hipMemcpyHostToDevice);
+    return d;
 }
 
 int stage_accel(int device, const Accel &acc, StagedAccel *out, int *fault = nullptr) {
-    StagedAccel a;
+    const std::vector<DQGrid> qbuf = pack_qnodes(acc);
     hipError_t err = hipSetDevice(device);
-    auto upload = [&err, fault](auto **dst, const auto &vec) {
-        using T = typename std::remove_reference<decltype(vec)>::type::value_type;
-        size_t n = vec.empty() ? 1 : vec.size();
-        if (err == hipSuccess && fault && *fault > 0 && (*fault)-- == 1) err = hipErrorOutOfMemory;
-        if (err == hipSuccess) err = hipMalloc((void **)dst, n * sizeof(T));
-        if (err == hipSuccess && !vec.empty())
-            err = hipMemcpy(*dst, vec.data(), vec.size() * sizeof(T), hipMemcpyHostToDevice);
-    };
-    upload(&a.nodes, acc.cnodes);
-    upload(&a.leaf, acc.leaf);
-    upload(&a.lin, acc.lin);
-    upload(&a.march, acc.march);
-    upload(&a.boxes, acc.boxes);
-    if (err == hipSuccess && !acc.qnodes.empty()) {  // the grid, then the quantized layouts
-        DQGrid g{};
-        for (int k = 0; k < 3; k++) g.g0[k] = acc.qg0[k], g.gs[k] = acc.qgs[k];
-        g.bound = acc.qbound;
-        const size_t nb = acc.qnodes.size() * sizeof(DNodeQ);
-        if (fault && *fault > 0 && (*fault)-- == 1) err = hipErrorOutOfMemory;
-        // (one node of padding past the last layout, then the one-shape leaves' records: qleaf_offset)
-        const size_t ro = qleaf_offset(acc.nodes_per_octant()), rb = acc.qleaves.size() * sizeof(DLeafRec);
-        if (err == hipSuccess) err = hipMalloc((void **)&a.qnodes, ro + rb);
-        if (err == hipSuccess) err = hipMemset((char *)(a.qnodes + 1) + nb, 0, sizeof(DNodeQ));
-        if (err == hipSuccess) err = hipMemcpy(a.qnodes, &g, sizeof g, hipMemcpyHostToDevice);
-        if (err == hipSuccess) err = hipMemcpy(a.qnodes + 1, acc.qnodes.data(), nb, hipMemcpyHostToDevice);
-        if (err == hipSuccess && rb)
-            err = hipMemcpy((char *)a.qnodes + ro, acc.qleaves.data(), rb, hipMemcpyHostToDevice);
-    }
+    // (the allocations in this order, the quantized buffer last when there is one: the test hook counts them)
+    const DNodeC *nodes = upload(err, acc.cnodes, fault);
+    const int32_t *leaf = upload(err, acc.leaf, fault);
+    const int32_t *lin = upload(err, acc.lin, fault);
+    const int32_t *march = upload(err, acc.march, fault);
+    const DBox *boxes = upload(err, acc.boxes, fault);
+    const DQGrid *qnodes = qbuf.empty() ? nullptr : upload(err, qbuf, fault);
+    StagedAccel a{};
+    view_set_accel(a, acc, nodes, qnodes, leaf, lin, march, boxes);
     if (err != hipSuccess) {
         free_staged(device, a);
         return hip_fail(err, "uploading the acceleration structure");
     }
-    a.nnodes = acc.nodes_per_octant();  // nodes per octant layout
-    a.nlin = (int)acc.lin.size();
-    a.nmarch = (int)acc.march.size();
-    a.bvh_bound = acc.bvh_bound;
     *out = a;
     return PT_OK;
 }
@@ -398,18 +379,8 @@ int stage_accel(int device, const Accel &acc, StagedAccel *out, int *fault = nul
 int commit_accel(GpuShare &g, StagedAccel &a) {
     HIP_TRY(hipSetDevice(g.device));
     HIP_TRY(hipDeviceSynchronize());
-    DeviceScene &d = g.ds;
-    StagedAccel old{d.nodes, d.qnodes, d.leaf, d.lin, d.march, d.boxes, d.nnodes, d.nlin, d.nmarch, d.bvh_bound};
-    d.nodes = a.nodes;
-    d.qnodes = a.qnodes;
-    d.leaf = a.leaf;
-    d.lin = a.lin;
-    d.march = a.march;
-    d.boxes = a.boxes;
-    d.nnodes = a.nnodes;
-    d.nlin = a.nlin;
-    d.nmarch = a.nmarch;
-    d.bvh_bound = a.bvh_bound;
+    StagedAccel old = g.ds.view;
+    view_set_accel(g.ds.view, a);
     a = StagedAccel{};
     free_staged(g.device, old);
     return PT_OK;
@@ -421,40 +392,27 @@ int init_share(GpuShare &g, int device, const Scene &S, const Accel &acc, const 
     g.device = device;
     HIP_TRY(hipSetDevice(device));
     hipError_t err = hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking);
-    auto upload = [&err](auto **dst, const auto &vec) {
-        using T = typename std::remove_reference<decltype(vec)>::type::value_type;
-        size_t n = vec.empty() ? 1 : vec.size();
-        if (err == hipSuccess) err = hipMalloc((void **)dst, n * sizeof(T));
-        if (err == hipSuccess && !vec.empty())
-            err = hipMemcpy(*dst, vec.data(), vec.size() * sizeof(T), hipMemcpyHostToDevice);
-    };
-    upload(&g.ds.shapes, hs);
-    upload(&g.ds.mats, hm);
-    if (!S.textures.empty()) {
-        upload(&g.ds.tex, S.textures);
-        upload(&g.ds.perlin, S.perlins);
-        upload(&g.ds.images, S.images);
-        upload(&g.ds.pixels, S.pixels);
-    }
+    const DShape *shapes = upload(err, hs);
+    const DMaterial *mats = upload(err, hm);
+    const bool tex = !S.textures.empty();
+    const DTexture *textures = tex ? upload(err, S.textures) : nullptr;
+    const DPerlin *perlins = tex ? upload(err, S.perlins) : nullptr;
+    const DImage *images = tex ? upload(err, S.images) : nullptr;
+    const uint8_t *pixels = tex ? upload(err, S.pixels) : nullptr;
+    view_set_scene(g.ds.view, S, shapes, mats, textures, perlins, images, pixels);
     if (err == hipSuccess) err = hipEventCreateWithFlags(&g.shard_ev, hipEventDisableTiming);
     // device counters: [0] march guard drops, [1] stop-gated launches that found the frame stopped, [2] of those,
     // launches that still had work (pt_render_stop_stats)
-    if (err == hipSuccess) err = hipMalloc((void **)&g.ds.guard, 4 * sizeof(unsigned long long));
-    if (err == hipSuccess) err = hipMemset(g.ds.guard, 0, 4 * sizeof(unsigned long long));
+    if (err == hipSuccess) err = hipMalloc((void **)&g.ds.view.guard, 4 * sizeof(unsigned long long));
+    if (err == hipSuccess) err = hipMemset(g.ds.view.guard, 0, 4 * sizeof(unsigned long long));
     if (err != hipSuccess) return hip_fail(err, "uploading the scene");
-    StagedAccel a;
+    StagedAccel a{};
     if (int rc = stage_accel(device, acc, &a)) return rc;
     if (int rc = commit_accel(g, a)) return rc;
     g.ws.tune = tuning_defaults();
-    g.ds.diag = g.ws.tune.diag;
+    g.ds.view.diag = g.ws.tune.diag;
     g.ds.nshapes = (int)hs.size();
-    g.ds.nmats = (int)hm.size();
-    g.ds.ext = S.textures.empty() ? 0 : 1;
-    for (const auto &h : S.shapes)
-        if (h.type == TORUS) g.ds.ext = 1;
-    g.ds.fkind = 0;  // Heart-only kernel builds unless another function is marched
-    for (const auto &h : S.shapes)
-        if (h.type == MARCH && h.func != 0) g.ds.fkind = -1;
+    g.ds.fkind = scene_builds(S).fkind;
     return PT_OK;
 }
 
@@ -473,15 +431,7 @@ int sync_all(pt_renderer *r) {
 
 FrameParams frame_params(const pt_renderer *r, const pt_camera &cam, uint32_t w, uint32_t h, uint32_t spp,
                          uint64_t seed) {
-    FrameParams P;
-    std::memset(&P, 0, sizeof P);
-    caster_params(cam, w, h, &P);
-    P.s11 = r->s11;
-    P.seed = seed;
-    P.width = w;
-    P.height = h;
-    P.spp = spp;
-    P.depth = r->depth;
+    FrameParams P = pt::frame_params(cam, w, h, spp, r->depth, seed, r->s11);
     P.rank = 0;
     P.world = 1;
     P.tiles_x = tiles_x_of(w);
@@ -765,7 +715,7 @@ int pt_renderer_set_option(pt_renderer *r, const char *name, int64_t value) {
         HIP_TRY(hipSetDevice(g.device));
         HIP_TRY(hipDeviceSynchronize());
         g.ws.tune = t;
-        g.ds.diag = t.diag;
+        g.ds.view.diag = t.diag;
     }
     return PT_OK;
 }
@@ -773,7 +723,7 @@ int pt_renderer_set_option(pt_renderer *r, const char *name, int64_t value) {
 int pt_renderer_get_option(const pt_renderer *r, const char *name, int64_t *value) {
     if (!r || !name || !value) return fail(PT_ERR_INVALID, "null argument");
     if (!std::strcmp(name, "bvh_nodes")) {  // read-only state
-        *value = r->gpus[0].ds.nnodes;
+        *value = r->gpus[0].ds.view.nnodes;
         return PT_OK;
     }
     if (!tuning_get(r->gpus[0].ws.tune, name, value)) return fail(PT_ERR_INVALID, std::string("unknown option: ") + name);
@@ -1110,8 +1060,8 @@ int pt_march_guard_drops(pt_renderer *r, uint64_t *count) {
         HIP_TRY(hipSetDevice(g.device));
         HIP_TRY(hipDeviceSynchronize());  // frames on any stream of the device
         unsigned long long n = 0;
-        HIP_TRY(hipMemcpy(&n, g.ds.guard, sizeof n, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemset(g.ds.guard, 0, sizeof n));
+        HIP_TRY(hipMemcpy(&n, g.ds.view.guard, sizeof n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemset(g.ds.view.guard, 0, sizeof n));
         total += n;
     }
     *count = total;
@@ -1126,8 +1076,8 @@ int pt_render_stop_stats(pt_renderer *r, uint64_t *skipped, uint64_t *worked) {
         HIP_TRY(hipSetDevice(g.device));
         HIP_TRY(hipDeviceSynchronize());
         unsigned long long c[2] = {0, 0};
-        HIP_TRY(hipMemcpy(c, g.ds.guard + 1, sizeof c, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemset(g.ds.guard + 1, 0, sizeof c));
+        HIP_TRY(hipMemcpy(c, g.ds.view.guard + 1, sizeof c, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemset(g.ds.view.guard + 1, 0, sizeof c));
         s += c[0];
         w += c[1];
     }

@@ -326,28 +326,19 @@ PT_HD uint32_t tile_logical(uint32_t p, uint32_t tiles_x, uint32_t world) {
     return ty * tiles_x + (p % tiles_x + tiles_x - ty % tiles_x) % tiles_x;
 }
 
-struct Scene {
-    const DShape *__restrict__ shapes;
-    const DMaterial *__restrict__ mats;
-    const DNodeC *__restrict__ nodes;  // compact form (pt_types.hpp)
-    const DQGrid *__restrict__ qnodes;  // quantized form after its grid (large trees; else null)
-    const int32_t *__restrict__ leaf;
-    const int32_t *__restrict__ lin;
-    const int32_t *__restrict__ march;
-    const DBox *__restrict__ boxes;
-    const DTexture *__restrict__ tex;  // non-solid texture trees (null when the scene has none)
-    const DPerlin *__restrict__ perlin;
-    const DImage *__restrict__ images;
-    const uint8_t *__restrict__ pixels;
-    int nnodes, nlin, nmarch, diag;  // diag bit 0: skip marched shapes (timing ablation only)
-    int nmats;
-    int ext;  // the scene needs the extended (EXT) builds: non-solid textures or a Torus
-    float bvh_bound;  // >= |every BVH node plane| (the f32 slab's error bound)
-    // marches dropped by the march guard (pt_march.hpp MARCH_GUARD), counted
-    // on the device (pt_march_guard_drops); null: not counted
-    unsigned long long *guard;
-};
-
+// Ray i of an array of 6 doubles per ray (origin, direction), and colour i of one of 3 doubles per colour: the
+// probes' and the host harnesses' arguments.
+PT_HD Ray load_ray(const double *rays, size_t i) {
+    Ray r;
+    r.o = v3(rays[i * 6 + 0], rays[i * 6 + 1], rays[i * 6 + 2]);
+    r.d = v3(rays[i * 6 + 3], rays[i * 6 + 4], rays[i * 6 + 5]);
+    return r;
+}
+PT_HD void store_rgb(double *out, size_t i, V3 c) {
+    out[i * 3 + 0] = c.x;
+    out[i * 3 + 1] = c.y;
+    out[i * 3 + 2] = c.z;
+}
 
 // Padded-box slab test against [min_t, max_t] (conservative: boxes are padded
 // far beyond the rounding of this test).
@@ -887,7 +878,7 @@ PT_HD V3 decided_leaf(int who, const Ray &ray) { return who >= 0 ? v3(0.0, 0.0, 
 // path ends, with the leaf radiance in *leaf; otherwise advances ray/depth.
 // Everything in a bounce after the closest hit (who, t) is known.
 // Stack: any type with push(id), pop() and a count n (IdStack in registers,
-// or the wavefront engine's per-slot id array in HBM).
+// or MemStack in memory: the wavefront engine's per-slot stacks in HBM).
 // EXT: the build for scenes with non-solid textures or a Torus (textured albedos are
 // evaluated at the hit and pushed by value; textured lights emit their value).
 template <bool STATS = false, int FK = march::F_ANY, bool EXT = false, class Stack>
@@ -956,15 +947,6 @@ PT_HD bool shade(const Scene &sc, int who, double t, Ray &ray, uint32_t &depth, 
     return false;
 }
 
-template <int NW, bool STATS = false, bool EXT = false>
-PT_HD bool bounce(const Scene &sc, Ray &ray, uint32_t &depth, IdStack<NW> &stk, Rng &rng, double s11, V3 *leaf,
-                  Ctr *ct = nullptr) {
-    double t;
-    if (STATS) ct->c[C_BOUNCES]++;
-    int who = closest<STATS, EXT>(sc, ray, T_MIN, __builtin_inf(), &t, ct);
-    return shade<STATS, march::F_ANY, EXT>(sc, who, t, ray, depth, stk, rng, s11, leaf, ct);
-}
-
 template <bool STATS = false, bool EXT = false, class Stack>
 PT_HD V3 unwind(const Scene &sc, Stack &stk, V3 c, Ctr *ct = nullptr) {
     while (stk.n > 0) {
@@ -981,54 +963,39 @@ PT_HD V3 unwind(const Scene &sc, Stack &stk, V3 c, Ctr *ct = nullptr) {
     return c;
 }
 
-// ray_color (src/renderer/mod.rs:23-45), iterative with the recursion's product order.
-// vb, vs: the textured-attenuation area of this lane (EXT builds).
-template <int NW, bool EXT = false>
-PT_HD V3 ray_color(const Scene &sc, Ray ray, uint32_t depth, Rng &rng, double s11, double *vb = nullptr,
-                   size_t vs = 0) {
-    IdStack<NW> stk;
-    stk.clear();
-    stk.vb = vb;
-    stk.vs = vs;
-    V3 leaf;
-    while (!bounce<NW, false, EXT>(sc, ray, depth, stk, rng, s11, &leaf)) {
-    }
-    return unwind<false, EXT>(sc, stk, leaf);
-}
-
-// The attenuation stack of one path in memory, for depths beyond IdStack's registers (depth > 64): id k at
-// ids[k * stride], a textured value of level k, component c at vb[(k * 3 + c) * stride] (EXT builds).  The caller
-// provides `depth` ids (a path pushes at most one per bounce) and depth levels of values.
-struct MemIdStack {
-    uint32_t *ids;
-    double *vb;
+// The attenuation stack of one path in memory: id k at base[k * stride], a textured value of level k, component c
+// at vb[(k * 3 + c) * stride] (EXT builds).  A push writes one 32-bit id (once, where the recursion would have
+// pushed it); the ids are read back only when the path ends (unwind).  The wavefront engine's per-slot stacks in
+// HBM and the deep probe's (depth > MAX_REG_DEPTH) are this type; the caller provides `depth` levels (a path
+// pushes at most one per bounce).
+struct MemStack {
+    uint32_t *base;
     size_t stride;
     int n;
+    double *vb;
     PT_HD void push_val(V3 a) {
-        vb[((size_t)n * 3 + 0) * stride] = a.x;
-        vb[((size_t)n * 3 + 1) * stride] = a.y;
-        vb[((size_t)n * 3 + 2) * stride] = a.z;
+        vb[(size_t)(n * 3 + 0) * stride] = a.x;
+        vb[(size_t)(n * 3 + 1) * stride] = a.y;
+        vb[(size_t)(n * 3 + 2) * stride] = a.z;
         push(VAL_BIT);
     }
     PT_HD V3 val(int level) const {
-        return v3(vb[((size_t)level * 3 + 0) * stride], vb[((size_t)level * 3 + 1) * stride],
-                  vb[((size_t)level * 3 + 2) * stride]);
+        return v3(vb[(size_t)(level * 3 + 0) * stride], vb[(size_t)(level * 3 + 1) * stride],
+                  vb[(size_t)(level * 3 + 2) * stride]);
     }
     PT_HD void push(uint32_t id) {
-        ids[(size_t)n * stride] = id;
+        base[(size_t)n * stride] = id;
         n++;
     }
     PT_HD uint32_t pop() {
         n--;
-        return ids[(size_t)n * stride];
+        return base[(size_t)n * stride];
     }
 };
 
-// ray_color with the stack in memory: the same bounces and the same product order as ray_color<NW>, at any depth.
-template <bool EXT = false>
-PT_HD V3 ray_color_mem(const Scene &sc, Ray ray, uint32_t depth, Rng &rng, double s11, uint32_t *ids, double *vb,
-                       size_t stride) {
-    MemIdStack stk{ids, vb, stride, 0};
+// ray_color (src/renderer/mod.rs:23-45), iterative with the recursion's product order, over either stack type.
+template <bool EXT, class Stack>
+PT_HD V3 ray_color_on(const Scene &sc, Ray ray, uint32_t depth, Rng &rng, double s11, Stack &stk) {
     V3 leaf;
     for (;;) {
         double t;
@@ -1036,6 +1003,23 @@ PT_HD V3 ray_color_mem(const Scene &sc, Ray ray, uint32_t depth, Rng &rng, doubl
         if (shade<false, march::F_ANY, EXT>(sc, who, t, ray, depth, stk, rng, s11, &leaf)) break;
     }
     return unwind<false, EXT>(sc, stk, leaf);
+}
+// with the stack in registers (depth <= 2 * NW).  vb, vs: the textured-attenuation area of this lane (EXT builds).
+template <int NW, bool EXT = false>
+PT_HD V3 ray_color(const Scene &sc, Ray ray, uint32_t depth, Rng &rng, double s11, double *vb = nullptr,
+                   size_t vs = 0) {
+    IdStack<NW> stk;
+    stk.clear();
+    stk.vb = vb;
+    stk.vs = vs;
+    return ray_color_on<EXT>(sc, ray, depth, rng, s11, stk);
+}
+// with the stack in memory: the same bounces and the same product order, at any depth.
+template <bool EXT = false>
+PT_HD V3 ray_color_mem(const Scene &sc, Ray ray, uint32_t depth, Rng &rng, double s11, uint32_t *ids, double *vb,
+                       size_t stride) {
+    MemStack stk{ids, stride, 0, vb};
+    return ray_color_on<EXT>(sc, ray, depth, rng, s11, stk);
 }
 
 // Camera sample: MultisamplerRayCaster::next (ray_caster.rs:103-118), u then v.

@@ -91,9 +91,7 @@ __global__ __launch_bounds__(256) void closest_hit_probe(dev::Scene sc, const do
                                   double max_t, pt_hit *__restrict__ out) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Ray r;
-    r.o = dev::v3(rays[i * 6 + 0], rays[i * 6 + 1], rays[i * 6 + 2]);
-    r.d = dev::v3(rays[i * 6 + 3], rays[i * 6 + 4], rays[i * 6 + 5]);
+    const Ray r = dev::load_ray(rays, i);
     double t;
     int who = dev::closest<false, true>(sc, r, min_t, max_t, &t);
     pt_hit h = {};
@@ -121,19 +119,15 @@ __global__ __launch_bounds__(256) void ray_color_probe(dev::Scene sc, const doub
                                 size_t n, uint32_t depth, double s11, double *__restrict__ out, double *vals) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Ray r;
-    r.o = dev::v3(rays[i * 6 + 0], rays[i * 6 + 1], rays[i * 6 + 2]);
-    r.d = dev::v3(rays[i * 6 + 3], rays[i * 6 + 4], rays[i * 6 + 5]);
+    const Ray r = dev::load_ray(rays, i);
     dev::Rng rng{states[i]};
     V3 c = vals ? dev::ray_color<NW, true>(sc, r, depth, rng, s11, vals + i, n) : dev::ray_color<NW>(sc, r, depth, rng, s11);
     states[i] = rng.s;
-    out[i * 3 + 0] = c.x;
-    out[i * 3 + 1] = c.y;
-    out[i * 3 + 2] = c.z;
+    dev::store_rgb(out, i, c);
 }
 
 // The probe at depths beyond the register stacks (depth > MAX_REG_DEPTH): the id stack in memory, lane i's id k at
-// ids[k * n + i] (dev::MemIdStack), the same bounces and product order.
+// ids[k * n + i] (dev::MemStack), the same bounces and product order.
 template <bool EXT>
 __global__ __launch_bounds__(256) void ray_color_probe_deep(dev::Scene sc, const double *__restrict__ rays,
                                                             uint64_t *__restrict__ states, size_t n, uint32_t depth,
@@ -141,15 +135,11 @@ __global__ __launch_bounds__(256) void ray_color_probe_deep(dev::Scene sc, const
                                                             double *vals) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Ray r;
-    r.o = dev::v3(rays[i * 6 + 0], rays[i * 6 + 1], rays[i * 6 + 2]);
-    r.d = dev::v3(rays[i * 6 + 3], rays[i * 6 + 4], rays[i * 6 + 5]);
+    const Ray r = dev::load_ray(rays, i);
     dev::Rng rng{states[i]};
     V3 c = dev::ray_color_mem<EXT>(sc, r, depth, rng, s11, ids + i, EXT ? vals + i : nullptr, n);
     states[i] = rng.s;
-    out[i * 3 + 0] = c.x;
-    out[i * 3 + 1] = c.y;
-    out[i * 3 + 2] = c.z;
+    dev::store_rgb(out, i, c);
 }
 
 template <int NW>
@@ -161,9 +151,7 @@ __global__ __launch_bounds__(256) void trace_pixels_probe(dev::Scene sc, FramePa
     V3 c = vals ? dev::trace_pixel<NW, false, false, march::F_ANY, true>(sc, P, idx % P.width, idx / P.width, nullptr,
                                                                          nullptr, vals + i, n)
                 : dev::trace_pixel<NW>(sc, P, idx % P.width, idx / P.width);
-    out[i * 3 + 0] = c.x;
-    out[i * 3 + 1] = c.y;
-    out[i * 3 + 2] = c.z;
+    dev::store_rgb(out, i, c);
 }
 
 // Diagnostic build: the same path with per-lane event counters (STATS), summed
@@ -249,31 +237,6 @@ __global__ __launch_bounds__(256, 2) void render_tiles_timed(dev::Scene sc, Fram
 }
 
 // ------------------------------------------------------------- launchers
-static dev::Scene dscene(const DeviceScene &s) {
-    dev::Scene d;
-    d.shapes = s.shapes;
-    d.mats = s.mats;
-    d.nodes = s.nodes;
-    d.qnodes = s.qnodes;
-    d.leaf = s.leaf;
-    d.lin = s.lin;
-    d.march = s.march;
-    d.boxes = s.boxes;
-    d.tex = s.tex;
-    d.perlin = s.perlin;
-    d.images = s.images;
-    d.pixels = s.pixels;
-    d.ext = s.ext;
-    d.nnodes = s.nnodes;
-    d.bvh_bound = s.bvh_bound;
-    d.nlin = s.nlin;
-    d.nmarch = s.nmarch;
-    d.nmats = s.nmats;
-    d.diag = s.diag;
-    d.guard = s.guard;
-    return d;
-}
-
 // The probes' builds by attenuation-stack width (builds::stack_words, pt_builds.hpp): every launcher below sends a
 // call deeper than MAX_REG_DEPTH elsewhere (the memory-stack probe) or refuses it.
 #define PT_DISPATCH_NW(depth, CALL)                                        \
@@ -291,12 +254,12 @@ hipError_t launch_render(const DeviceScene &s, const FrameParams &P, double *out
     if (P.tile_count == 0) return hipSuccess;
     ws.refusal[0] = 0;
     builds::Inputs in{};
-    in.ext = s.ext != 0;
+    in.ext = s.view.ext != 0;
     in.fkind = s.fkind;
-    in.nnodes = s.nnodes;
-    in.nmarch = s.nmarch;
-    in.has_qnodes = s.qnodes != nullptr;
-    in.scene_diag = s.diag;
+    in.nnodes = s.view.nnodes;
+    in.nmarch = s.view.nmarch;
+    in.has_qnodes = s.view.qnodes != nullptr;
+    in.scene_diag = s.view.diag;
     in.depth = P.depth;
     in.samples = (uint64_t)P.tile_count * TILE * TILE * P.spp;
     in.window = P.s_begin > 0 || (P.s_end && P.s_end < P.spp);
@@ -306,13 +269,13 @@ hipError_t launch_render(const DeviceScene &s, const FrameParams &P, double *out
     in.tune = ws.tune;
     const builds::Choice ch = builds::choose(in);
     if (ch.engine == builds::REFUSE) return hipErrorInvalidValue;
-    if (ch.engine == builds::WAVE) return launch_render_wave(dscene(s), P, out, st, &ws, ch);
+    if (ch.engine == builds::WAVE) return launch_render_wave(s.view, P, out, st, &ws, ch);
     hipError_t e0 = timer_begin(ws.timer, st, K_MEGA);
     if (e0 != hipSuccess) return e0;
     bool launched = false;
 #define X(NW, WAVES, FK)                                                             \
     if (ch.mega.is(NW, WAVES, FK)) {                                                 \
-        render_tiles<NW, WAVES, FK><<<P.tile_count, 256, 0, st>>>(dscene(s), P, out); \
+        render_tiles<NW, WAVES, FK><<<P.tile_count, 256, 0, st>>>(s.view, P, out);   \
         launched = true;                                                             \
     }
     PT_MEGA_BUILDS(X)
@@ -344,53 +307,44 @@ hipError_t launch_encode_rgba8(const double *rgb, size_t p0, size_t p1, uint8_t 
 hipError_t launch_closest_hit(const DeviceScene &s, const double *rays, size_t n, double min_t, double max_t,
                               pt_hit *out, hipStream_t st) {
     if (!n) return hipSuccess;
-    closest_hit_probe<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(dscene(s), rays, n, min_t, max_t, out);
+    closest_hit_probe<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(s.view, rays, n, min_t, max_t, out);
     return hipGetLastError();
 }
 
-// Stream-ordered scratch for the probes' textured attenuation values (textured
-// scenes only): n lanes x (depth + 1) levels x 3 doubles.
-struct ProbeVals {
-    double *p = nullptr;
+// Stream-ordered scratch of the probes, freed on the stream when the launcher returns.
+template <class T>
+struct Scratch {
+    T *p = nullptr;
     hipStream_t st;
-    hipError_t alloc(const DeviceScene &s, size_t n, uint32_t depth) {
-        if (!s.ext) return hipSuccess;
-        return hipMallocAsync((void **)&p, n * ((size_t)depth + 1) * 3 * sizeof(double), st);
-    }
-    ~ProbeVals() {
+    hipError_t alloc(size_t count) { return hipMallocAsync((void **)&p, count * sizeof(T), st); }
+    ~Scratch() {
         if (p) (void)hipFreeAsync(p, st);
     }
 };
-// The same for a deep probe's id stacks: n lanes x depth ids.
-struct ProbeIds {
-    uint32_t *p = nullptr;
-    hipStream_t st;
-    hipError_t alloc(size_t n, uint32_t depth) {
-        return hipMallocAsync((void **)&p, n * (size_t)depth * sizeof(uint32_t), st);
-    }
-    ~ProbeIds() {
-        if (p) (void)hipFreeAsync(p, st);
-    }
-};
+// The probes' textured attenuation values (scenes that need the extended builds only): n lanes x (depth + 1) levels
+// x 3 doubles.
+static hipError_t alloc_vals(Scratch<double> &vals, const DeviceScene &s, size_t n, uint32_t depth) {
+    return s.view.ext ? vals.alloc(n * ((size_t)depth + 1) * 3) : hipSuccess;
+}
 
 hipError_t launch_ray_color(const DeviceScene &s, const double *rays, uint64_t *states, size_t n, uint32_t depth,
                             double s11, double *out, hipStream_t st) {
     if (!n) return hipSuccess;
-    ProbeVals vals{nullptr, st};
-    hipError_t e = vals.alloc(s, n, depth);
+    Scratch<double> vals{nullptr, st};
+    hipError_t e = alloc_vals(vals, s, n, depth);
     if (e != hipSuccess) return e;
     if (depth > MAX_REG_DEPTH) {
-        ProbeIds ids{nullptr, st};
-        if ((e = ids.alloc(n, depth)) != hipSuccess) return e;
+        Scratch<uint32_t> ids{nullptr, st};  // the id stacks: n lanes x depth ids
+        if ((e = ids.alloc(n * (size_t)depth)) != hipSuccess) return e;
         const unsigned blocks = (unsigned)((n + 255) / 256);
-        if (s.ext)
-            ray_color_probe_deep<true><<<blocks, 256, 0, st>>>(dscene(s), rays, states, n, depth, s11, out, ids.p, vals.p);
+        if (s.view.ext)
+            ray_color_probe_deep<true><<<blocks, 256, 0, st>>>(s.view, rays, states, n, depth, s11, out, ids.p, vals.p);
         else
-            ray_color_probe_deep<false><<<blocks, 256, 0, st>>>(dscene(s), rays, states, n, depth, s11, out, ids.p, nullptr);
+            ray_color_probe_deep<false><<<blocks, 256, 0, st>>>(s.view, rays, states, n, depth, s11, out, ids.p, nullptr);
         return hipGetLastError();
     }
     PT_DISPATCH_NW(depth, (ray_color_probe<NW><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(
-                              dscene(s), rays, states, n, depth, s11, out, vals.p)));
+                              s.view, rays, states, n, depth, s11, out, vals.p)));
     return hipGetLastError();
 }
 
@@ -398,11 +352,11 @@ hipError_t launch_trace_pixels(const DeviceScene &s, const FrameParams &P, const
                                double *out, hipStream_t st) {
     if (!n) return hipSuccess;
     if (P.depth > MAX_REG_DEPTH) return hipErrorNotSupported;  // (register id stacks only)
-    ProbeVals vals{nullptr, st};
-    hipError_t e = vals.alloc(s, n, P.depth);
+    Scratch<double> vals{nullptr, st};
+    hipError_t e = alloc_vals(vals, s, n, P.depth);
     if (e != hipSuccess) return e;
     PT_DISPATCH_NW(P.depth, (trace_pixels_probe<NW><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(
-                                dscene(s), P, pixels, n, out, vals.p)));
+                                s.view, P, pixels, n, out, vals.p)));
     return hipGetLastError();
 }
 
@@ -410,10 +364,10 @@ hipError_t launch_count_work(const DeviceScene &s, const FrameParams &P, const u
                              unsigned long long *ctr, hipStream_t st) {
     if (!n) return hipSuccess;
     if (P.depth > MAX_REG_DEPTH) return hipErrorNotSupported;  // (register id stacks only)
-    ProbeVals vals{nullptr, st};
-    hipError_t e = vals.alloc(s, n, P.depth);
+    Scratch<double> vals{nullptr, st};
+    hipError_t e = alloc_vals(vals, s, n, P.depth);
     if (e != hipSuccess) return e;
-    PT_DISPATCH_NW(P.depth, (count_work<NW><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(dscene(s), P, pixels, n,
+    PT_DISPATCH_NW(P.depth, (count_work<NW><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(s.view, P, pixels, n,
                                                                                          ctr, vals.p)));
     return hipGetLastError();
 }
@@ -428,8 +382,8 @@ hipError_t launch_march_probe(const double *jobs, size_t n, double *t, int32_t *
 hipError_t launch_render_timed(const DeviceScene &s, const FrameParams &P, double *out, unsigned long long *acc,
                                hipStream_t st) {
     if (P.tile_count == 0) return hipSuccess;
-    if (s.ext) return hipErrorNotSupported;  // the timing build has no extended (texture / Torus) build
-    render_tiles_timed<<<P.tile_count, 256, 0, st>>>(dscene(s), P, out, acc);
+    if (s.view.ext) return hipErrorNotSupported;  // the timing build has no extended (texture / Torus) build
+    render_tiles_timed<<<P.tile_count, 256, 0, st>>>(s.view, P, out, acc);
     return hipGetLastError();
 }
 

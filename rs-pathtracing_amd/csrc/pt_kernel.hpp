@@ -8,23 +8,12 @@
 
 namespace pt {
 
+// One device's scene: the kernels' view of its buffers (dev::Scene, filled by view_set_scene / view_set_accel,
+// pt_accel.hpp; this owns the buffers, view_buffers), and what the choice of builds needs beside it.
 struct DeviceScene {
-    DShape *shapes = nullptr;
-    DMaterial *mats = nullptr;
-    DNodeC *nodes = nullptr;
-    DQGrid *qnodes = nullptr;  // the quantized layouts after their grid (large trees only; else null)
-    int32_t *leaf = nullptr, *lin = nullptr, *march = nullptr;
-    DBox *boxes = nullptr;
-    DTexture *tex = nullptr;  // non-solid textures (null when the scene has none)
-    DPerlin *perlin = nullptr;
-    DImage *images = nullptr;
-    uint8_t *pixels = nullptr;
-    int nshapes = 0, nmats = 0, nnodes = 0, nlin = 0, nmarch = 0;
-    float bvh_bound = 0.f;  // Accel::bvh_bound
-    int ext = 0;    // non-solid textures or a Torus: the extended (EXT) kernel builds
-    int fkind = 0;  // 0: every marched shape is a Heart (or none) -> Heart-only kernel builds; -1: any
-    int diag = 0;  // Tuning::diag (timing ablation), copied here for the probes
-    unsigned long long *guard = nullptr;  // device counter of marches dropped by the march guard
+    dev::Scene view = {};
+    int nshapes = 0;
+    int fkind = 0;  // scene_builds(): 0: every marched shape is a Heart (or none) -> Heart-only kernel builds; -1: any
 };
 
 // Per-kernel launch timing (pt_kernel_timing): HIP events recorded on the

@@ -188,6 +188,20 @@ void caster_params(const pt_camera &c, uint32_t width, uint32_t height, FramePar
     fp->pixel_resolution = vw / (double)width;
 }
 
+FrameParams frame_params(const pt_camera &cam, uint32_t width, uint32_t height, uint32_t spp, uint32_t depth,
+                         uint64_t seed, double s11) {
+    FrameParams P;
+    std::memset(&P, 0, sizeof P);
+    caster_params(cam, width, height, &P);
+    P.s11 = s11;
+    P.seed = seed;
+    P.width = width;
+    P.height = height;
+    P.spp = spp;
+    P.depth = depth;
+    return P;
+}
+
 // UniformFloat::new_inclusive (rand 0.8.5 distributions/uniform.rs)
 double uniform_incl_scale(double lo, double hi) {
     const double max_rand = 1.0 - 2.220446049250313e-16;
@@ -199,6 +213,15 @@ double uniform_incl_scale(double lo, double hi) {
         std::memcpy(&scale, &b, 8);
     }
     return scale;
+}
+
+SceneBuilds scene_builds(const Scene &sc) {
+    SceneBuilds b{sc.textures.empty() ? 0 : 1, 0};
+    for (const auto &h : sc.shapes) {
+        if (h.type == TORUS) b.ext = 1;
+        if (h.type == MARCH && h.func != 0) b.fkind = -1;
+    }
+    return b;
 }
 
 DShape to_device(const HostShape &s) {

@@ -68,10 +68,22 @@ void camera_new(const double pos[3], const double dir[3], const double up[3], do
 // Fills the caster part of FrameParams (pos/right/up/left_top/pixel_resolution).
 void caster_params(const pt_camera &cam, uint32_t width, uint32_t height, FrameParams *fp);
 
+// A frame's constants for one camera: the caster part and the sample counts; the tile shard (rank .. s_end) and
+// the stop flag stay zero for the caller to set.
+FrameParams frame_params(const pt_camera &cam, uint32_t width, uint32_t height, uint32_t spp, uint32_t depth,
+                         uint64_t seed, double s11);
+
 // RNG spec: SplitMix64 finaliser, keyed per (pixel, sample).
 uint64_t mix64(uint64_t z);
 uint64_t sample_key(uint64_t seed, uint64_t pixel, uint64_t sample);
 double uniform_incl_scale(double lo, double hi);
+
+// The kernel builds a realized scene needs.  ext: 1 with any non-solid texture or any Torus (the extended builds).
+// fkind: 0 when every marched shape is a Heart, or none is marched (the Heart-only builds); -1 otherwise (any).
+struct SceneBuilds {
+    int ext, fkind;
+};
+SceneBuilds scene_builds(const Scene &sc);
 
 DShape to_device(const HostShape &s);
 DMaterial to_device(const HostMaterial &m);

@@ -154,6 +154,33 @@ struct Ctr {
     uint64_t c[C_COUNT];
 };
 
+// What every kernel and device function reads of a scene: the one view of the device buffers (or, in the host
+// builds of the tests and tools, of host vectors).  The megakernel and the probes take it by value, so its layout is
+// their kernel-argument layout.  Only view_set_scene and view_set_accel (pt_accel.hpp) fill it.
+namespace dev {
+struct Scene {
+    const DShape *__restrict__ shapes;
+    const DMaterial *__restrict__ mats;
+    const DNodeC *__restrict__ nodes;  // compact form (DNodeC)
+    const DQGrid *__restrict__ qnodes;  // quantized form after its grid (large trees; else null)
+    const int32_t *__restrict__ leaf;
+    const int32_t *__restrict__ lin;
+    const int32_t *__restrict__ march;
+    const DBox *__restrict__ boxes;
+    const DTexture *__restrict__ tex;  // non-solid texture trees (null when the scene has none)
+    const DPerlin *__restrict__ perlin;
+    const DImage *__restrict__ images;
+    const uint8_t *__restrict__ pixels;
+    int nnodes, nlin, nmarch, diag;  // diag bit 0: skip marched shapes (timing ablation only)
+    int nmats;
+    int ext;  // the scene needs the extended (EXT) builds: non-solid textures or a Torus
+    float bvh_bound;  // >= |every BVH node plane| (the f32 slab's error bound)
+    // marches dropped by the march guard (pt_march.hpp MARCH_GUARD), counted
+    // on the device (pt_march_guard_drops); null: not counted
+    unsigned long long *guard;
+};
+}  // namespace dev
+
 constexpr double T_MIN = 0.001;  // ray_color: closest_hit(ray, 0.001, INF), src/renderer/mod.rs:24
 
 }  // namespace pt

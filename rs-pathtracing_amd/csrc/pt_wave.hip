@@ -53,6 +53,7 @@
 
 namespace pt {
 
+using dev::MemStack;
 using dev::Ray;
 using dev::V3;
 
@@ -155,34 +156,6 @@ __device__ __forceinline__ const T &kargs(const T *p) {
 __device__ __forceinline__ uint32_t lane_id() {
     return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
 }
-
-// The attenuation-id stack of a path kept in HBM: a push writes one 32-bit
-// id (once, where the recursion would have pushed it); the ids are read back
-// only when the path ends (unwind).
-struct MemStack {
-    uint32_t *base;
-    size_t stride;
-    int n;
-    double *vb;  // textured attenuation values: level k, component c at vb[(k * 3 + c) * stride]
-    __device__ __forceinline__ void push_val(V3 a) {
-        vb[(size_t)(n * 3 + 0) * stride] = a.x;
-        vb[(size_t)(n * 3 + 1) * stride] = a.y;
-        vb[(size_t)(n * 3 + 2) * stride] = a.z;
-        push(dev::VAL_BIT);
-    }
-    __device__ __forceinline__ V3 val(int level) const {
-        return dev::v3(vb[(size_t)(level * 3 + 0) * stride], vb[(size_t)(level * 3 + 1) * stride],
-                       vb[(size_t)(level * 3 + 2) * stride]);
-    }
-    __device__ __forceinline__ void push(uint32_t id) {
-        base[(size_t)n * stride] = id;
-        n++;
-    }
-    __device__ __forceinline__ uint32_t pop() {
-        n--;
-        return base[(size_t)n * stride];
-    }
-};
 
 // dev::unwind for an HBM id stack, with the loads batched: the top UB ids are
 // loaded together, then their albedos together, then multiplied in the

@@ -1,6 +1,6 @@
 // Test-only host build of the deep path (depth > 64): ray_color with the attenuation-id stack in memory
-// (dev::MemIdStack through dev::shade and dev::unwind, pt_device.hpp), the code ray_color_probe_deep runs on the
-// GPU, on a scene realized as path_harness.cpp does.  tests/test_deep_host.py compares it with the oracle bit for
+// (dev::MemStack through dev::shade and dev::unwind, pt_device.hpp: the one memory stack, the type of the wavefront
+// engine's per-slot stacks of every frame and of ray_color_probe_deep), on a scene realized as path_harness.cpp does.  tests/test_deep_host.py compares it with the oracle bit for
 // bit.  With DEEP_HARNESS_MAIN it is a stand-alone program (for a sanitizer build): it also walks the plan of deep
 // frames (pt_plan.hpp).  Never used by the product.
 #include <cstdio>
@@ -18,13 +18,11 @@ extern "C" void h_ray_color_mem(void *p, const double *rays, uint64_t *states, s
     std::vector<uint32_t> ids(n * (size_t)depth + 1);
     std::vector<double> vals(n * ((size_t)depth + 1) * 3);
     for (size_t i = 0; i < n; i++) {
-        dev::Ray r;
-        r.o = dev::v3(rays[i * 6 + 0], rays[i * 6 + 1], rays[i * 6 + 2]);
-        r.d = dev::v3(rays[i * 6 + 3], rays[i * 6 + 4], rays[i * 6 + 5]);
+        const dev::Ray r = dev::load_ray(rays, i);
         dev::Rng rng{states[i]};
         const dev::V3 c = dev::ray_color_mem<true>(b->view, r, depth, rng, b->s11, ids.data() + i, vals.data() + i, n);
         states[i] = rng.s;
-        out[i * 3 + 0] = c.x, out[i * 3 + 1] = c.y, out[i * 3 + 2] = c.z;
+        dev::store_rgb(out, i, c);
     }
 }
 

@@ -16,7 +16,7 @@ using namespace pt;
 struct Bundle {
     Scene sc;
     Accel acc;
-    std::vector<DQGrid> qbuf;  // the quantized layouts after their grid, as the device buffer (DQGrid-aligned)
+    std::vector<DQGrid> qbuf;  // pack_qnodes: the quantized nodes' buffer as the device holds it
     std::vector<DShape> shapes;
     std::vector<DMaterial> mats;
     dev::Scene view;
@@ -25,40 +25,14 @@ struct Bundle {
 
 extern "C" void *h_scene_new(const char *json, size_t len, int random_spheres, uint64_t seed) {
     try {
-        Bundle *b = new Bundle();  // value-initialised: every dev::Scene field not set below is 0 (cancel: none)
+        Bundle *b = new Bundle();  // value-initialised: diag 0, no guard counter
         b->sc = scene_from_json(json, len, random_spheres != 0, seed);
         b->acc = build_accel(b->sc, b->sc.json_shapes);
         for (auto &s : b->sc.shapes) b->shapes.push_back(to_device(s));
         for (auto &m : b->sc.materials) b->mats.push_back(to_device(m));
-        b->view.shapes = b->shapes.data();
-        b->view.mats = b->mats.data();
-        b->view.nodes = b->acc.cnodes.data();
-        b->view.leaf = b->acc.leaf.data();
-        b->view.lin = b->acc.lin.data();
-        b->view.march = b->acc.march.data();
-        b->view.boxes = b->acc.boxes.data();
-        const bool tex = !b->sc.textures.empty();
-        b->view.tex = tex ? b->sc.textures.data() : nullptr;
-        b->view.perlin = tex ? b->sc.perlins.data() : nullptr;
-        b->view.images = tex ? b->sc.images.data() : nullptr;
-        b->view.pixels = tex ? b->sc.pixels.data() : nullptr;
         if (b->acc.qnodes.empty() && !b->acc.nodes.empty()) build_qnodes(b->acc, b->sc);  // (small trees too)
-        if (!b->acc.qnodes.empty()) {
-            const size_t nb = b->acc.qnodes.size() * sizeof(DNodeQ);
-            const size_t ro = qleaf_offset(b->acc.nodes_per_octant()), rb = b->acc.qleaves.size() * sizeof(DLeafRec);
-            b->qbuf.resize((ro + rb + sizeof(DQGrid) - 1) / sizeof(DQGrid) + 1);  // (+ padding, the leaf records)
-            if (rb) std::memcpy((char *)b->qbuf.data() + ro, b->acc.qleaves.data(), rb);
-            DQGrid &g = b->qbuf[0];
-            for (int k = 0; k < 3; k++) g.g0[k] = b->acc.qg0[k], g.gs[k] = b->acc.qgs[k];
-            g.bound = b->acc.qbound;
-            std::memcpy(&b->qbuf[1], b->acc.qnodes.data(), nb);
-            b->view.qnodes = b->qbuf.data();
-        }
-        b->view.nnodes = b->acc.nodes_per_octant();
-        b->view.bvh_bound = b->acc.bvh_bound;
-        b->view.nlin = (int)b->acc.lin.size();
-        b->view.nmarch = (int)b->acc.march.size();
-        b->view.diag = 0;
+        b->qbuf = pack_qnodes(b->acc);
+        view_of_host(b->view, b->sc, b->acc, b->shapes, b->mats, b->qbuf);
         b->s11 = uniform_incl_scale(-1.0, 1.0);
         return b;
     } catch (...) {
@@ -72,6 +46,62 @@ extern "C" void h_accel_stats(void *p, int *out) {
     out[1] = (int)b->acc.lin.size();
     out[2] = (int)b->acc.march.size();
     out[3] = (int)b->acc.leaf.size();
+}
+
+// pack_qnodes against a restatement of the buffer's layout (the steps the library's upload took before it had the
+// packer): a zeroed buffer of qleaf_offset + records bytes, the grid at 0, the layouts copied behind it (the node
+// after them stays zero: the walk's padding), the records copied to qleaf_offset.  Returns 0 when both hold the
+// same bytes; out: the packed bytes, nodes per octant, quantized nodes, records.
+extern "C" int h_pack_check(void *p, uint64_t *out) {
+    Bundle *b = (Bundle *)p;
+    const Accel &a = b->acc;
+    out[0] = b->qbuf.size() * sizeof(DQGrid);
+    out[1] = (uint64_t)a.nodes_per_octant();
+    out[2] = a.qnodes.size();
+    out[3] = a.qleaves.size();
+    if (a.qnodes.empty()) return b->qbuf.empty() ? 0 : 1;
+    const size_t nb = a.qnodes.size() * sizeof(DNodeQ);
+    const size_t ro = qleaf_offset(a.nodes_per_octant()), rb = a.qleaves.size() * sizeof(DLeafRec);
+    if (ro < sizeof(DQGrid) + nb + sizeof(DNodeQ)) return 2;  // (no room for the padding node)
+    std::vector<unsigned char> want(ro + rb, 0);
+    DQGrid g{};
+    for (int k = 0; k < 3; k++) g.g0[k] = a.qg0[k], g.gs[k] = a.qgs[k];
+    g.bound = a.qbound;
+    std::memcpy(want.data(), &g, sizeof g);
+    std::memcpy(want.data() + sizeof g, a.qnodes.data(), nb);
+    if (rb) std::memcpy(want.data() + ro, a.qleaves.data(), rb);
+    if (want.size() != out[0]) return 3;
+    return std::memcmp(want.data(), b->qbuf.data(), want.size()) ? 4 : 0;
+}
+// 1 when the same tree without its quantized nodes packs to nothing
+extern "C" int h_pack_empty_without_qnodes(void *p) {
+    Accel a = ((Bundle *)p)->acc;
+    a.qnodes.clear();
+    return pack_qnodes(a).empty() ? 1 : 0;
+}
+
+// The view as view_set_scene / view_set_accel left it.  Returns the pointers that are not "null exactly when the
+// vector is empty"; ints: pairs of (view, Accel / Scene) for nnodes, nlin, nmarch, nmats, then scene_builds' ext
+// and fkind and the view's ext; bounds: the view's and the Accel's bvh_bound.
+extern "C" int h_view_check(void *p, int *ints, float *bounds) {
+    Bundle *b = (Bundle *)p;
+    const dev::Scene &v = b->view;
+    const Accel &a = b->acc;
+    const Scene &sc = b->sc;
+    const bool got[12] = {v.shapes != nullptr, v.mats != nullptr,  v.nodes != nullptr,  v.qnodes != nullptr,
+                          v.leaf != nullptr,   v.lin != nullptr,   v.march != nullptr,  v.boxes != nullptr,
+                          v.tex != nullptr,    v.perlin != nullptr, v.images != nullptr, v.pixels != nullptr};
+    const bool want[12] = {!b->shapes.empty(), !b->mats.empty(),    !a.cnodes.empty(),  !b->qbuf.empty(),
+                           !a.leaf.empty(),    !a.lin.empty(),      !a.march.empty(),   !a.boxes.empty(),
+                           !sc.textures.empty(), !sc.perlins.empty(), !sc.images.empty(), !sc.pixels.empty()};
+    int bad = 0;
+    for (int k = 0; k < 12; k++) bad += got[k] != want[k];
+    const int vals[11] = {v.nnodes, a.nodes_per_octant(), v.nlin,  (int)a.lin.size(),       v.nmarch, (int)a.march.size(),
+                          v.nmats,  (int)sc.materials.size(), scene_builds(sc).ext, scene_builds(sc).fkind, v.ext};
+    for (int k = 0; k < 11; k++) ints[k] = vals[k];
+    bounds[0] = v.bvh_bound;
+    bounds[1] = a.bvh_bound;
+    return bad;
 }
 
 // Device node form against the host nodes: each f32 box must contain the f64
@@ -149,9 +179,7 @@ extern "C" int h_qnode_check(void *p) {
 extern "C" int h_closest(void *p, const double *ray, double min_t, double max_t, double *t, double *point,
                          double *normal, int *front) {
     Bundle *b = (Bundle *)p;
-    dev::Ray r;
-    r.o = dev::v3(ray[0], ray[1], ray[2]);
-    r.d = dev::v3(ray[3], ray[4], ray[5]);
+    const dev::Ray r = dev::load_ray(ray, 0);
     int who = dev::closest(b->view, r, min_t, max_t, t);
     if (who >= 0) {
         dev::Hit h = dev::finish(b->shapes[who], r, *t);
@@ -164,36 +192,26 @@ extern "C" int h_closest(void *p, const double *ray, double min_t, double max_t,
 
 extern "C" void h_ray_color(void *p, const double *ray, uint64_t *state, uint32_t depth, double *out) {
     Bundle *b = (Bundle *)p;
-    dev::Ray r;
-    r.o = dev::v3(ray[0], ray[1], ray[2]);
-    r.d = dev::v3(ray[3], ray[4], ray[5]);
+    const dev::Ray r = dev::load_ray(ray, 0);
     dev::Rng rng{*state};
     std::vector<double> vals((depth + 1) * 3);  // textured attenuation values of this one lane
     dev::V3 c = depth <= 8 ? dev::ray_color<4, true>(b->view, r, depth, rng, b->s11, vals.data(), 1)
                            : dev::ray_color<32, true>(b->view, r, depth, rng, b->s11, vals.data(), 1);
     *state = rng.s;
-    out[0] = c.x, out[1] = c.y, out[2] = c.z;
+    dev::store_rgb(out, 0, c);
 }
 
 extern "C" void h_trace_pixels(void *p, uint32_t w, uint32_t h, uint32_t spp, uint32_t depth, uint64_t seed,
                                const uint32_t *pixels, size_t n, double *out) {
     Bundle *b = (Bundle *)p;
-    FrameParams P;
-    std::memset(&P, 0, sizeof P);
-    caster_params(b->sc.camera, w, h, &P);
-    P.s11 = b->s11;
-    P.seed = seed;
-    P.width = w;
-    P.height = h;
-    P.spp = spp;
-    P.depth = depth;
+    const FrameParams P = frame_params(b->sc.camera, w, h, spp, depth, seed, b->s11);
     std::vector<double> vals((depth + 1) * 3);
     for (size_t i = 0; i < n; i++) {
         dev::V3 c = depth <= 8 ? dev::trace_pixel<4, false, false, march::F_ANY, true>(
                                      b->view, P, pixels[i] % w, pixels[i] / w, nullptr, nullptr, vals.data(), 1)
                                : dev::trace_pixel<32, false, false, march::F_ANY, true>(
                                      b->view, P, pixels[i] % w, pixels[i] / w, nullptr, nullptr, vals.data(), 1);
-        out[3 * i] = c.x, out[3 * i + 1] = c.y, out[3 * i + 2] = c.z;
+        dev::store_rgb(out, i, c);
     }
 }
 
@@ -202,15 +220,7 @@ extern "C" void h_trace_pixels(void *p, uint32_t w, uint32_t h, uint32_t spp, ui
 extern "C" void h_count_work(void *p, uint32_t w, uint32_t h, uint32_t spp, uint32_t depth, uint64_t seed,
                              const uint32_t *pixels, size_t n, uint64_t *counters) {
     Bundle *b = (Bundle *)p;
-    FrameParams P;
-    std::memset(&P, 0, sizeof P);
-    caster_params(b->sc.camera, w, h, &P);
-    P.s11 = b->s11;
-    P.seed = seed;
-    P.width = w;
-    P.height = h;
-    P.spp = spp;
-    P.depth = depth;
+    const FrameParams P = frame_params(b->sc.camera, w, h, spp, depth, seed, b->s11);
     Ctr c;
     std::memset(&c, 0, sizeof c);
     std::vector<double> vals((depth + 1) * 3);
@@ -230,9 +240,7 @@ extern "C" void h_count_work(void *p, uint32_t w, uint32_t h, uint32_t spp, uint
 // FMA_SLAB bounce build for large BVHs).  Both must give the same (who, t).
 extern "C" int h_closest_nomarch(void *p, const double *ray, int fma, double *t) {
     Bundle *b = (Bundle *)p;
-    dev::Ray r;
-    r.o = dev::v3(ray[0], ray[1], ray[2]);
-    r.d = dev::v3(ray[3], ray[4], ray[5]);
+    const dev::Ray r = dev::load_ray(ray, 0);
     const dev::V3 inv = dev::v3(1.0 / r.d.x, 1.0 / r.d.y, 1.0 / r.d.z);
     double best = __builtin_inf();
     int who = -1;
@@ -254,9 +262,7 @@ extern "C" int h_walk_counts(void *p, const double *rays, size_t n, uint32_t *co
     Bundle *b = (Bundle *)p;
     if (!b->view.qnodes) return -1;
     for (size_t i = 0; i < n; i++) {
-        dev::Ray r;
-        r.o = dev::v3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]);
-        r.d = dev::v3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+        const dev::Ray r = dev::load_ray(rays, i);
         const dev::V3 inv = dev::v3(1.0 / r.d.x, 1.0 / r.d.y, 1.0 / r.d.z);
         Ctr c;
         std::memset(&c, 0, sizeof c);

@@ -1,6 +1,6 @@
-"""The deep path on the CPU: ray_color with the attenuation-id stack in memory (dev::MemIdStack through dev::shade
-and dev::unwind, pt_device.hpp: what ray_color_probe_deep runs on the GPU for depth > 64), compiled for the host from
-tests/native/deep_path_harness.cpp, against the oracle bit for bit on the closed room (scenes/deep_room.py).  The same
+"""The deep path on the CPU: ray_color with the attenuation-id stack in memory (dev::MemStack through dev::shade
+and dev::unwind, pt_device.hpp: the stack type of the wavefront engine's frames, and what ray_color_probe_deep runs on
+the GPU for depth > 64), compiled for the host from tests/native/deep_path_harness.cpp, against the oracle bit for bit on the closed room (scenes/deep_room.py).  The same
 harness as a stand-alone program under AddressSanitizer and UBSan covers the new host code (the stack, the plan of
 deep frames)."""
 import ctypes as C
@@ -93,7 +93,8 @@ def test_paths_really_run_deep():
 
 
 def test_memory_stack_equals_register_stack_up_to_64(H):
-    """Up to depth 64 the memory stack and the register stack (h_ray_color, IdStack<32>) give the same bits."""
+    """Up to depth 64 the memory stack (MemStack, the wavefront engine's) and the register stack (h_ray_color,
+    IdStack<32>) give the same bits."""
     text = R.room_json("textured")
     rays, states = rays_and_states(100, 3)
     raw = text.encode()

@@ -120,30 +120,12 @@ int main(int argc, char **argv) {
         std::vector<DMaterial> mats;
         for (auto &s : sc.shapes) shapes.push_back(to_device(s));
         for (auto &m : sc.materials) mats.push_back(to_device(m));
+        const std::vector<DQGrid> qbuf = pack_qnodes(acc);
         dev::Scene v{};
-        v.shapes = shapes.data();
-        v.mats = mats.data();
-        v.nodes = acc.cnodes.data();
-        v.leaf = acc.leaf.data();
-        v.lin = acc.lin.data();
-        v.march = acc.march.data();
-        v.boxes = acc.boxes.data();
-        v.nnodes = acc.nodes_per_octant();
-        v.nlin = (int)acc.lin.size();
-        v.nmarch = (int)acc.march.size();
+        view_of_host(v, sc, acc, shapes, mats, qbuf);
         const uint32_t W = 1920, H = 1080;
-        FrameParams P;
-        memset(&P, 0, sizeof P);
-        pt_camera cam;
-        memset(&cam, 0, sizeof cam);
-        cam = sc.camera;
-        caster_params(cam, W, H, &P);
-        P.s11 = uniform_incl_scale(-1.0, 1.0);
-        P.seed = 1;
-        P.width = W;
-        P.height = H;
-        P.spp = (uint32_t)atoi(argv[4]);
-        P.depth = 8;
+        const FrameParams P =
+            frame_params(sc.camera, W, H, (uint32_t)atoi(argv[4]), 8, 1, uniform_incl_scale(-1.0, 1.0));
         // <pixels>: a count (scattered sample) or a comma-separated pixel list
         std::vector<uint64_t> list;
         if (strchr(argv[3], ',')) {
