@@ -315,6 +315,43 @@ std::vector<DQGrid> pack_qnodes(const Accel &a) {
     return buf;
 }
 
+// Rectangles whose inverse transforms have one linear part next to each other: each rectangle that has not joined a
+// group yet opens one where it stands, and the later rectangles of the list with its nine entries follow it, marked.
+// The entries are compared as 64-bit patterns (+0 and -0 differ: the products with them differ in sign; a NaN equals
+// nothing).  transform_new builds inverse = (Si * Ri) * Ti, whose linear part depends on the rotation and the scale
+// alone, so the walls of a room and the faces of a box group whatever their places.  Any order gives the same hits
+// (the acceptance rule is order-independent), and the other shapes keep their places among themselves.
+void group_rectangles(std::vector<int32_t> &lin, const Scene &sc) {
+    constexpr int NW = 9;
+    auto row = [&](int32_t i, uint64_t (&w)[NW]) {
+        const DShape d = to_device(sc.shapes[i]);
+        bool ok = sc.shapes[i].type == RECTANGLE;
+        for (int k = 0; k < NW; k++) {
+            const double v = d.inv[4 * (k / 3) + k % 3];
+            std::memcpy(&w[k], &v, 8);
+            ok = ok && v == v;
+        }
+        return ok;
+    };
+    std::vector<int32_t> out;
+    std::vector<char> taken(lin.size(), 0);
+    out.reserve(lin.size());
+    for (size_t k = 0; k < lin.size(); k++) {
+        if (taken[k]) continue;
+        const int32_t i = lin[k] & LIN_ID_MASK;
+        out.push_back(i);
+        uint64_t w[NW], v[NW];
+        if (!row(i, w)) continue;
+        for (size_t j = k + 1; j < lin.size(); j++) {
+            const int32_t o = lin[j] & LIN_ID_MASK;
+            if (taken[j] || !row(o, v) || std::memcmp(w, v, sizeof w) != 0) continue;
+            taken[j] = 1;
+            out.push_back(o | LIN_GROUPED);
+        }
+    }
+    lin.swap(out);
+}
+
 Accel build_accel(const Scene &sc, int json_shapes, int leaf_max) {
     Accel a;
     a.boxes.reserve(sc.shapes.size());
@@ -351,6 +388,7 @@ Accel build_accel(const Scene &sc, int json_shapes, int leaf_max) {
         }
         rest.swap(keep);
     }
+    group_rectangles(a.lin, sc);
     if (!rest.empty()) {
         Builder b{a.boxes, a};
         b.leaf_max = std::max(1, std::min(16, leaf_max));

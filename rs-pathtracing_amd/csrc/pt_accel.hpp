@@ -35,7 +35,7 @@ struct Accel {
     std::vector<DNodeC> cnodes;  // the same nodes in the device form (f32 boxes rounded outward)
     int nodes_per_octant() const { return (int)(nodes.size() / BVH_OCTANTS); }
     std::vector<int32_t> leaf;   // shape ids referenced by leaf nodes
-    std::vector<int32_t> lin;    // wave-uniform list
+    std::vector<int32_t> lin;    // wave-uniform list (shape ids; LIN_GROUPED marks, pt_types.hpp)
     std::vector<int32_t> march;  // ray-marched shapes
     std::vector<DBox> boxes;     // padded world AABB per shape
     float bvh_bound = 0.f;  // >= |every plane of cnodes| (dev::Scene::bvh_bound)
@@ -51,6 +51,9 @@ constexpr int LIN_MAX = 32;  // JSON shape count up to which the JSON shapes for
 
 // leaf_max: shapes per BVH leaf (the renderer option "bvh_leaf")
 Accel build_accel(const Scene &sc, int json_shapes, int leaf_max = 1);
+// Orders a uniform list so that rectangles whose inverse transforms have the same linear part sit next to each
+// other, every one after a group's first marked LIN_GROUPED (build_accel does this to Accel::lin)
+void group_rectangles(std::vector<int32_t> &lin, const Scene &sc);
 // the quantized nodes of a's layouts (build_accel does this for trees of at least BIG_BVH_NODES nodes per layout;
 // tests call it for smaller ones)
 void build_qnodes(Accel &a, const Scene &sc);

@@ -408,11 +408,44 @@ PT_HD void closest_nomarch(const Scene &sc, const Ray &r, V3 inv, double min_t, 
     double best = *best_t;
     int who = *who_out;
     // wave-uniform list (few JSON shapes): scalar loads of each shape
+    // Parallel rectangles of one size class (walls, the faces of a room: inverse transforms with the same linear
+    // part, which build_accel puts next to each other, every one after the first marked LIN_GROUPED) multiply the
+    // ray by the same nine entries, and their object-space rays differ in the translation column only.  The first
+    // rectangle of a group leaves those products for the others: g_pz, g_ox, g_oy are oz, ox, oy before the last
+    // addition (of m[11], m[3], m[7]), g_dz, g_dx, g_dy the direction.  Each value is formed by shape_test's
+    // operations in shape_test's order, so every t is the one shape_test gives (C2 +1.6 %).
+    double g_pz = 0.0, g_dz = 1.0, g_ox = 0.0, g_oy = 0.0, g_dx = 0.0, g_dy = 0.0;
     for (int k = 0; k < ((PART & 1) ? sc.nlin : 0); k++) {
         if (any && wave_all(who >= 0)) break;
-        const int i = uniform_index(uniform_load(&sc.lin[k]));
+        const int entry = uniform_index(uniform_load(&sc.lin[k]));
+        const int i = entry & LIN_ID_MASK;
         const DShape s = uniform_shape(&sc.shapes[i]);
         PT_LP(ULIST_SHAPE);
+        if (s.type == RECTANGLE) {
+            if (STATS) ct->c[C_TEST_RECT]++;
+            const double *m = s.inv;
+            if (!(entry & LIN_GROUPED)) {
+                g_pz = r.o.x * m[8] + r.o.y * m[9] + r.o.z * m[10];
+                g_dz = r.d.x * m[8] + r.d.y * m[9] + r.d.z * m[10];
+                g_ox = r.o.x * m[0] + r.o.y * m[1] + r.o.z * m[2];
+                g_oy = r.o.x * m[4] + r.o.y * m[5] + r.o.z * m[6];
+                g_dx = r.d.x * m[0] + r.d.y * m[1] + r.d.z * m[2];
+                g_dy = r.d.x * m[4] + r.d.y * m[5] + r.d.z * m[6];
+            }
+            const double oz = g_pz + m[11];
+            const double tt = -oz / g_dz;
+            bool h = !(tt < min_t || tt > best);
+            if (h) {
+                PT_LP(RECT_ROWS);
+                const double px = (g_ox + m[3]) + g_dx * tt, py = (g_oy + m[7]) + g_dy * tt;
+                h = !(px < s.p[0] || px > s.p[2] || py < s.p[1] || py > s.p[3]);
+            }
+            if (h && (tt < best || i > who)) {
+                best = tt;
+                who = i;
+            }
+            continue;
+        }
         if (s.type == CUBE || s.type == SPHERE) {
             // the padded world box first (12 FLOP with the caller's 1/d):
             // a miss there is a miss of the exact test, which costs a full

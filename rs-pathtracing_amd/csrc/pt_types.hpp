@@ -181,6 +181,12 @@ struct Scene {
 };
 }  // namespace dev
 
+// An entry of the uniform list (Scene::lin) is a shape id below 2^30.  LIN_GROUPED marks a rectangle whose inverse
+// transform has the linear part (inv[0..2], [4..6], [8..10]) of the rectangle before it in the list, bit for bit:
+// the closest hit reuses that rectangle's products with the ray (closest_nomarch).
+constexpr int32_t LIN_GROUPED = 1 << 30;
+constexpr int32_t LIN_ID_MASK = LIN_GROUPED - 1;
+
 constexpr double T_MIN = 0.001;  // ray_color: closest_hit(ray, 0.001, INF), src/renderer/mod.rs:24
 
 }  // namespace pt
