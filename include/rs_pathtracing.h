@@ -243,6 +243,38 @@ uint32_t pt_shard_tiles(uint32_t width, uint32_t height, uint32_t rank, uint32_t
 int pt_unshard_device(int device, const double *d_gathered, uint32_t width, uint32_t height, uint32_t world,
                       double *d_frame, void *hip_stream);
 
+/* ---- first-hit guide planes (albedo, normal, depth) ---------------------- */
+/* What a denoiser, a compositor or a debugger wants beside the beauty frame
+ * (the reference renders none): the first hit of every camera sample of the
+ * frame (camera, width, height, samples_number, seed).  Sample s of pixel
+ * p = x + y*width is the primary ray of the beauty frame's sample s (its RNG
+ * key is pt_sample_key(seed, p, s); the camera draws u, then v), so the
+ * planes carry the frame's own jitter.  Each plane is width*height*3 doubles
+ * laid out like the colour buffer; each value is the in-order sum over the
+ * samples divided by samples_number once.
+ *   albedo: the first hit's colour.  Lambertian, Metal: the albedo (its
+ *     texture's value at the hit).  Dielectric: (1, 1, 1).  DiffuseLight: its
+ *     emit (or texture value), NOT clamped (a caller that wants [0, 1]
+ *     clamps).  EmptyMaterial: (0, 0, 0).  A miss: the background colour.
+ *   normal: the world normal of pt_hit (unit, turned against the ray); a miss
+ *     adds (0, 0, 0); the mean is not renormalised.
+ *   depth: [0] sum of t over the hitting samples / samples_number (t is the
+ *     world distance: directions are unit), [1] hits / samples_number (the
+ *     coverage), [2] the smallest t of the hitting samples, 0 when none hits.
+ * A pass of its own, independent of the renderer's depth, options and
+ * workspace; PT_ERR_INVALID when all planes are NULL, a size or
+ * samples_number is 0 or rank >= world; PT_ERR_STATE while a render_start
+ * frame is in flight.  (Library 0.4.3; no ABI change.) */
+/* First-hit guide planes of the frame pt_render_device(..., samples_number, seed, rank, world, ...) renders:
+ * same tiles, same shard layout, same per-sample camera rays.  Any of the three device pointers may be NULL
+ * (not all).  Queued on hip_stream on the renderer's first device; independent of the renderer's depth. */
+int pt_render_aov_device(pt_renderer *r, const pt_camera *camera, uint32_t width, uint32_t height,
+                         uint32_t samples_number, uint64_t seed, uint32_t rank, uint32_t world,
+                         double *d_albedo, double *d_normal, double *d_depth, void *hip_stream);
+/* The whole frame's planes into host buffers (w*h*3 doubles each, any may be NULL, not all); blocks. */
+int pt_render_aov(pt_renderer *r, const pt_camera *camera, uint32_t width, uint32_t height,
+                  uint32_t samples_number, uint64_t seed, double *albedo, double *normal, double *depth);
+
 /* ---- resumable frames (checkpoint / resume) ----------------------------- */
 /* The reference renders a frame in one go and keeps nothing between runs
  * (Renderer::render, src/renderer/mod.rs:67-114; its GUI saves only the

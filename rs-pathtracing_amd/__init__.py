@@ -50,6 +50,7 @@ EXPORTS = [
     "pt_kernel_timing", "pt_encode_rgba8", "pt_encode_rgba8_device", "pt_write_png", "pt_write_ppm",
     "pt_sample_key", "pt_last_error", "pt_version", "pt_abi_version", "pt_abi_layout", "pt_renderer_peer_access",
     "pt_render_device_samples", "pt_checkpoint_save", "pt_checkpoint_load",
+    "pt_render_aov_device", "pt_render_aov",
 ]
 ABI_VERSION = 4  # PT_ABI_VERSION this binding is written for
 
@@ -154,6 +155,8 @@ def lib():
         "pt_render_frame_device": (C.c_int, [vp, C.POINTER(CameraStruct), u32, u32, u32, u64, vp, vp]),
         "pt_render_device_samples": (C.c_int, [vp, C.POINTER(CameraStruct), u32, u32, u32, u64, u32, u32, u32, u32,
                                                vp, vp]),
+        "pt_render_aov_device": (C.c_int, [vp, C.POINTER(CameraStruct), u32, u32, u32, u64, u32, u32, vp, vp, vp, vp]),
+        "pt_render_aov": (C.c_int, [vp, C.POINTER(CameraStruct), u32, u32, u32, u64, d, d, d]),
         "pt_checkpoint_save": (C.c_int, [C.c_char_p, C.POINTER(CheckpointStruct), d]),
         "pt_checkpoint_load": (C.c_int, [C.c_char_p, C.POINTER(CheckpointStruct), d, u64]),
         "pt_shard_tiles": (u32, [u32, u32, u32, u32]),
@@ -423,6 +426,34 @@ class HipRenderer(Renderer):
         device), ordered after stream_ptr's queued work (pt_render_frame_device)."""
         _check(lib().pt_render_frame_device(self._h, C.byref(camera._c), width, height, spp, seed,
                                             C.c_void_p(frame_ptr), C.c_void_p(stream_ptr)))
+
+    # ---- first-hit guide planes (pt_render_aov) ------------------------
+    AOV_PLANES = ("albedo", "normal", "depth")
+
+    def render_aov(self, camera: Camera, img_params: ImageParams, samples_number: int, seed=None,
+                   planes=("albedo", "normal", "depth")) -> dict:
+        """The first-hit guide planes of the frame render(camera, img_params, samples_number, seed) renders (the
+        same per-sample camera rays): a dict of (w*h, 3) float64 arrays for the planes asked for.  albedo: the
+        first hit's colour (a miss: the background; a light's emit is not clamped); normal: the mean world normal
+        (a miss adds 0); depth: (sum t / spp, hits / spp, min t or 0).  See pt_render_aov."""
+        planes = tuple(planes)
+        if not planes or any(p not in self.AOV_PLANES for p in planes):
+            raise ValueError("planes must name at least one of %r" % (self.AOV_PLANES,))
+        s = self.seed if seed is None else int(seed)
+        out = {p: np.zeros((img_params.width * img_params.height, 3), dtype=np.float64) for p in planes}
+        ptr = [_dptr(out[p]) if p in out else None for p in self.AOV_PLANES]
+        _check(lib().pt_render_aov(self._h, C.byref(camera._c), img_params.width, img_params.height,
+                                   int(samples_number), s, *ptr))
+        return out
+
+    def render_aov_device(self, camera: Camera, width: int, height: int, spp: int, seed: int, rank: int,
+                          world: int, albedo_ptr: int, normal_ptr: int, depth_ptr: int, stream_ptr: int = 0):
+        """This rank's tiles of the guide planes into device memory (render_device's layout: the frame for
+        world == 1, else compact shards with pixels outside the frame 0) on the HIP stream stream_ptr; a pointer
+        of 0 leaves that plane out (not all three; see pt_render_aov_device)."""
+        _check(lib().pt_render_aov_device(self._h, C.byref(camera._c), width, height, spp, seed, rank, world,
+                                          C.c_void_p(albedo_ptr or None), C.c_void_p(normal_ptr or None),
+                                          C.c_void_p(depth_ptr or None), C.c_void_p(stream_ptr)))
 
     # ---- probes --------------------------------------------------------
     def closest_hit(self, rays: np.ndarray, min_t: float = 0.001, max_t: float = float("inf")) -> np.ndarray:

@@ -20,6 +20,7 @@
 
 #include "../../include/rs_pathtracing.h"
 #include "pt_accel.hpp"
+#include "pt_aov.hpp"
 #include "pt_kernel.hpp"
 #include "pt_plan.hpp"
 #include "pt_scene.hpp"
@@ -148,7 +149,7 @@ __attribute__((visibility("hidden"))) void pt_set_last_error(const char *msg) { 
 #define PT_SRC_SHA "unknown"
 #endif
 const char *pt_version(void) {
-    return "rs-pathtracing-amd 0.4.2 (gfx950, f64 megakernel + wavefront march engine; src " PT_SRC_SHA ")";
+    return "rs-pathtracing-amd 0.4.3 (gfx950, f64 megakernel + wavefront march engine; src " PT_SRC_SHA ")";
 }
 uint32_t pt_abi_version(void) { return PT_ABI_VERSION; }
 
@@ -937,6 +938,52 @@ int pt_render_frame_device(pt_renderer *r, const pt_camera *cam, uint32_t w, uin
     HIP_TRY(hipSetDevice(g0.device));
     HIP_TRY(hipEventRecord(g0.shard_ev, g0.stream));
     HIP_TRY(hipStreamWaitEvent(st, g0.shard_ev, 0));
+    return PT_OK;
+}
+
+// ---- first-hit guide planes (pt_aov.hpp): a pass beside the frame, on the first device ----
+namespace {
+int aov_args_refused(const pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t rank,
+                     uint32_t world, const double *a, const double *n, const double *d) {
+    if (!r || !cam) return fail(PT_ERR_INVALID, "null argument");
+    if (!a && !n && !d) return fail(PT_ERR_INVALID, "at least one of the albedo, normal and depth planes must be given");
+    if (w == 0 || h == 0 || spp == 0) return fail(PT_ERR_INVALID, "width, height and samples_number must be > 0");
+    if (world == 0 || rank >= world) return fail(PT_ERR_INVALID, "rank must be < world");
+    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
+    return PT_OK;
+}
+}  // namespace
+
+int pt_render_aov_device(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
+                         uint32_t rank, uint32_t world, double *d_albedo, double *d_normal, double *d_depth,
+                         void *stream) {
+    if (int rc = aov_args_refused(r, cam, w, h, spp, rank, world, d_albedo, d_normal, d_depth)) return rc;
+    GpuShare &g = r->gpus[0];
+    HIP_TRY(hipSetDevice(g.device));
+    // the frame's own parameters (pt_render_device's): the pass reads the camera, the seed and the tile deal of them
+    FrameParams P = frame_params(r, *cam, w, h, spp, seed);
+    P.rank = rank;
+    P.world = world;
+    P.compact = world > 1 ? 1 : 0;
+    P.tile_begin = 0;
+    P.tile_count = pt_shard_tiles(w, h, rank, world);
+    HIP_TRY(launch_aov(g.ds.view, P, d_albedo, d_normal, d_depth, (hipStream_t)stream));
+    return PT_OK;
+}
+
+int pt_render_aov(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
+                  double *albedo, double *normal, double *depth) {
+    if (int rc = aov_args_refused(r, cam, w, h, spp, 0, 1, albedo, normal, depth)) return rc;
+    HIP_TRY(hipSetDevice(r->device()));
+    const size_t count = (size_t)w * h * 3;
+    double *host[3] = {albedo, normal, depth};
+    DevBuf<double> dev[3];  // staging of the wanted planes, freed on return
+    for (int k = 0; k < 3; k++)
+        if (host[k]) HIP_TRY(dev[k].alloc(count));
+    if (int rc = pt_render_aov_device(r, cam, w, h, spp, seed, 0, 1, dev[0].p, dev[1].p, dev[2].p, r->stream())) return rc;
+    HIP_TRY(hipStreamSynchronize(r->stream()));
+    for (int k = 0; k < 3; k++)
+        if (host[k]) HIP_TRY(hipMemcpy(host[k], dev[k].p, count * sizeof(double), hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

@@ -4,7 +4,7 @@
 // (src/bin/main.rs:71-83, 281-289).  This does the same in one go, on the GPU:
 //
 //   pt_render scene.json [spp [w h]] [-d depth] [-s seed] [-o image.png|image.ppm] [-f frame.f64]
-//             [-c checkpoint -n window_spp [-x windows]]
+//             [-c checkpoint -n window_spp [-x windows]] [-a prefix]
 //
 // -o: the encoded image (PNG, or PPM by extension; default rendered.png, the name of the reference's "F" save).
 // -f: the linear f64 frame (w*h*3, row-major), for comparisons.
@@ -12,6 +12,10 @@
 //     running sums go to the checkpoint file; a run that finds the file resumes from it (same scene, camera,
 //     depth, size, spp and seed, else it refuses).  -x stops after that many windows of this run (exit status 3,
 //     the checkpoint kept): an interruption, for tests.  The finished frame is bit-identical to a run without -c.
+// -a: the frame's first-hit guide planes (pt_render_aov: the same samples' camera rays), written after the frame as
+//     prefix.albedo.png (the display encode), prefix.normal.png ((n + 1) / 2 per channel, linear, x 255.999) and
+//     prefix.depth.png (grey: mean t / coverage over the frame's largest such value; black where nothing is hit);
+//     with -f also the three raw planes, albedo then normal then depth, as prefix.aov.f64.
 // Exit status: 0 done, 1 error (the library's message on stderr), 2 usage, 3 stopped with a checkpoint.
 #include <hip/hip_runtime_api.h>
 
@@ -32,7 +36,7 @@ namespace {
 int usage() {
     std::fprintf(stderr,
                  "usage: pt_render scene.json [spp [w h]] [-d depth] [-s seed] [-o image.png|.ppm] [-f frame.f64]\n"
-                 "                 [-c checkpoint -n window_spp [-x windows]]\n");
+                 "                 [-c checkpoint -n window_spp [-x windows]] [-a aov_prefix]\n");
     return 2;
 }
 
@@ -58,6 +62,15 @@ uint64_t fnv(uint64_t h, const void *p, size_t n) {
     return h;
 }
 
+bool write_doubles(const std::string &path, const std::vector<double> &v) {
+    FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f || std::fwrite(v.data(), sizeof(double), v.size(), f) != v.size() || std::fclose(f) != 0) {
+        std::fprintf(stderr, "pt_render: cannot write %s\n", path.c_str());
+        return false;
+    }
+    return true;
+}
+
 bool ends_with(const std::string &s, const char *suf) {
     const size_t n = std::strlen(suf);
     return s.size() >= n && s.compare(s.size() - n, n, suf) == 0;
@@ -69,7 +82,7 @@ int main(int argc, char **argv) {
     std::vector<const char *> pos;
     uint32_t depth = 50, window = 0, stop_after = 0;
     uint64_t seed = 1;
-    std::string out_img = "rendered.png", out_f64, ckpt;
+    std::string out_img = "rendered.png", out_f64, ckpt, aov;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto val = [&](const char *name) -> const char * {
@@ -85,6 +98,7 @@ int main(int argc, char **argv) {
         else if (a == "-f") out_f64 = val("-f");
         else if (a == "-c") ckpt = val("-c");
         else if (a == "-n") window = (uint32_t)std::strtoul(val("-n"), nullptr, 10);
+        else if (a == "-a") aov = val("-a");
         else if (a == "-x") stop_after = (uint32_t)std::strtoul(val("-x"), nullptr, 10);
         else if (a.size() > 1 && a[0] == '-') return usage();
         else pos.push_back(argv[i]);
@@ -170,19 +184,42 @@ int main(int argc, char **argv) {
         (void)hipFree(d_out);
         std::remove(ckpt.c_str());
     }
-    if (!out_f64.empty()) {
-        FILE *f = std::fopen(out_f64.c_str(), "wb");
-        if (!f || std::fwrite(rgb.data(), sizeof(double), rgb.size(), f) != rgb.size() || std::fclose(f) != 0) {
-            std::fprintf(stderr, "pt_render: cannot write %s\n", out_f64.c_str());
-            return 1;
-        }
-    }
+    if (!out_f64.empty() && !write_doubles(out_f64, rgb)) return 1;
     if (!out_img.empty()) {
         std::vector<uint8_t> rgba(npix * 4);
         if ((rc = pt_encode_rgba8(rgb.data(), npix, rgba.data()))) return fail("encode", rc);
         rc = ends_with(out_img, ".ppm") ? pt_write_ppm(out_img.c_str(), rgba.data(), w, h)
                                         : pt_write_png(out_img.c_str(), rgba.data(), w, h);
         if (rc) return fail(out_img.c_str(), rc);
+    }
+    if (!aov.empty()) {
+        std::vector<double> planes(npix * 9);
+        double *alb = planes.data(), *nrm = alb + npix * 3, *dep = nrm + npix * 3;
+        if ((rc = pt_render_aov(r, &cam, w, h, spp, seed, alb, nrm, dep))) return fail("guide planes", rc);
+        if (!out_f64.empty() && !write_doubles(aov + ".aov.f64", planes)) return 1;
+        std::vector<uint8_t> rgba(npix * 4);
+        auto save = [&](const char *plane) {
+            const std::string path = aov + "." + plane + ".png";
+            const int e = pt_write_png(path.c_str(), rgba.data(), w, h);
+            return e ? fail(path.c_str(), e) : 0;
+        };
+        if ((rc = pt_encode_rgba8(alb, npix, rgba.data()))) return fail("encode", rc);
+        if (save("albedo")) return 1;
+        auto byte = [](double v) { return (uint8_t)(v > 0.0 ? (v < 1.0 ? v * 255.999 : 255.0) : 0.0); };  // NaN -> 0
+        for (size_t i = 0; i < npix; i++) {
+            for (int c = 0; c < 3; c++) rgba[i * 4 + c] = byte((nrm[i * 3 + c] + 1.0) / 2.0);
+            rgba[i * 4 + 3] = 255;
+        }
+        if (save("normal")) return 1;
+        double far = 0.0;  // the largest mean distance of the hitting samples (mean t / coverage)
+        for (size_t i = 0; i < npix; i++)
+            if (dep[i * 3 + 1] > 0.0 && dep[i * 3] / dep[i * 3 + 1] > far) far = dep[i * 3] / dep[i * 3 + 1];
+        for (size_t i = 0; i < npix; i++) {
+            const uint8_t g = dep[i * 3 + 1] > 0.0 && far > 0.0 ? byte(dep[i * 3] / dep[i * 3 + 1] / far) : 0;
+            rgba[i * 4 + 0] = rgba[i * 4 + 1] = rgba[i * 4 + 2] = g;
+            rgba[i * 4 + 3] = 255;
+        }
+        if (save("depth")) return 1;
     }
     std::printf("rendered %ux%u at %u spp, depth %u\n", w, h, spp, depth);
     pt_renderer_destroy(r);
