@@ -275,6 +275,46 @@ int pt_render_aov_device(pt_renderer *r, const pt_camera *camera, uint32_t width
 int pt_render_aov(pt_renderer *r, const pt_camera *camera, uint32_t width, uint32_t height,
                   uint32_t samples_number, uint64_t seed, double *albedo, double *normal, double *depth);
 
+/* ---- guided denoiser for the beauty frame and its guide planes ---------- */
+/* An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a whole
+ * frame (world == 1 layout: width*height*3 doubles each, all finite): the
+ * colour, and the albedo, normal and depth planes of pt_render_aov (of depth
+ * only [0], the mean t, is read).  f64, no transcendental function, sums in a
+ * fixed order: the result is the same bits on every run and equals the numpy
+ * restatement in tests/denoiseref.py.  The filter, step by step, is in
+ * rs-pathtracing_amd/csrc/pt_denoise.hpp and DESIGN.md 3.8: the colour is
+ * divided by the albedo (PT_DENOISE_DEMODULATE; a channel <= 1e-3 divides by
+ * 1), filtered `iterations` times with a 5x5 kernel at strides 1, 2, 4, ...
+ * whose taps are weighted by the distance of normals (sigma_normal), of depth
+ * relative to the pixel's own (sigma_depth) and, when sigma_colour > 0, of
+ * the filtered colours (sigma_colour / stride), and multiplied by the albedo
+ * again.
+ * Defaults: 5 iterations, sigma_normal 0.5, sigma_depth 0.1, sigma_colour 0,
+ * flags PT_DENOISE_DEMODULATE.  sigma_colour 0 switches the colour term off,
+ * and it is off by default: without a variance estimate it keeps a 4-spp
+ * frame's fireflies.  +inf is a legal sigma and means that term weighs 1.
+ * d_out == d_rgb is allowed; no other overlap is.  d_albedo may be NULL only
+ * without PT_DENOISE_DEMODULATE.  PT_ERR_INVALID: a NULL required pointer, a
+ * zero size, iterations outside 1..PT_DENOISE_MAX_ITERATIONS, an unknown flag
+ * bit, sigma_normal or sigma_depth not greater than 0 or NaN, sigma_colour
+ * below 0 or NaN, a d_work that is not 16-byte aligned, a frame of more than
+ * 2^31 - 1 tiles of 16x16.  A refused call writes nothing.  Sharded frames
+ * (world > 1) are denoised after pt_unshard_device.  (Library 0.4.3; no ABI
+ * change.) */
+#define PT_DENOISE_DEMODULATE 1u
+#define PT_DENOISE_MAX_ITERATIONS 8
+/* doubles of device workspace pt_denoise_device needs for a width x height frame (0 if either is 0) */
+size_t pt_denoise_workspace_doubles(uint32_t width, uint32_t height);
+/* queued on hip_stream of HIP device `device` (-1 = current), like pt_encode_rgba8_device; needs no renderer */
+int pt_denoise_device(int device, const double *d_rgb, const double *d_albedo, const double *d_normal,
+                      const double *d_depth, uint32_t width, uint32_t height, uint32_t iterations,
+                      double sigma_normal, double sigma_depth, double sigma_colour, uint32_t flags,
+                      double *d_out, double *d_work, void *hip_stream);
+/* the same from and to host buffers; allocates, copies, blocks */
+int pt_denoise(int device, const double *rgb, const double *albedo, const double *normal, const double *depth,
+               uint32_t width, uint32_t height, uint32_t iterations, double sigma_normal, double sigma_depth,
+               double sigma_colour, uint32_t flags, double *out);
+
 /* ---- resumable frames (checkpoint / resume) ----------------------------- */
 /* The reference renders a frame in one go and keeps nothing between runs
  * (Renderer::render, src/renderer/mod.rs:67-114; its GUI saves only the

@@ -51,7 +51,10 @@ EXPORTS = [
     "pt_sample_key", "pt_last_error", "pt_version", "pt_abi_version", "pt_abi_layout", "pt_renderer_peer_access",
     "pt_render_device_samples", "pt_checkpoint_save", "pt_checkpoint_load",
     "pt_render_aov_device", "pt_render_aov",
+    "pt_denoise_workspace_doubles", "pt_denoise_device", "pt_denoise",
 ]
+DENOISE_DEMODULATE = 1  # PT_DENOISE_DEMODULATE
+DENOISE_MAX_ITERATIONS = 8  # PT_DENOISE_MAX_ITERATIONS
 ABI_VERSION = 4  # PT_ABI_VERSION this binding is written for
 
 
@@ -157,6 +160,10 @@ def lib():
                                                vp, vp]),
         "pt_render_aov_device": (C.c_int, [vp, C.POINTER(CameraStruct), u32, u32, u32, u64, u32, u32, vp, vp, vp, vp]),
         "pt_render_aov": (C.c_int, [vp, C.POINTER(CameraStruct), u32, u32, u32, u64, d, d, d]),
+        "pt_denoise_workspace_doubles": (sz, [u32, u32]),
+        "pt_denoise_device": (C.c_int, [C.c_int, vp, vp, vp, vp, u32, u32, u32, C.c_double, C.c_double, C.c_double,
+                                        u32, vp, vp, vp]),
+        "pt_denoise": (C.c_int, [C.c_int, d, d, d, d, u32, u32, u32, C.c_double, C.c_double, C.c_double, u32, d]),
         "pt_checkpoint_save": (C.c_int, [C.c_char_p, C.POINTER(CheckpointStruct), d]),
         "pt_checkpoint_load": (C.c_int, [C.c_char_p, C.POINTER(CheckpointStruct), d, u64]),
         "pt_shard_tiles": (u32, [u32, u32, u32, u32]),
@@ -628,6 +635,48 @@ def encode_rgba8_device(rgb_ptr: int, npix: int, rgba_ptr: int, stream_ptr: int 
     """The display encode on the GPU (pt_encode_rgba8_device): device pointers."""
     _check(lib().pt_encode_rgba8_device(int(device), C.c_void_p(rgb_ptr), int(npix), C.c_void_p(rgba_ptr),
                                         C.c_void_p(stream_ptr)))
+
+
+def denoise_workspace_doubles(width: int, height: int) -> int:
+    """Doubles of device workspace denoise_device needs for a width x height frame (pt_denoise_workspace_doubles)."""
+    return int(lib().pt_denoise_workspace_doubles(int(width), int(height)))
+
+
+def denoise_device(rgb_ptr: int, albedo_ptr: int, normal_ptr: int, depth_ptr: int, width: int, height: int,
+                   out_ptr: int, work_ptr: int, iterations: int = 5, sigma_normal: float = 0.5,
+                   sigma_depth: float = 0.1, sigma_colour: float = 0.0, demodulate: bool = True, stream_ptr: int = 0,
+                   device: int = -1):
+    """The guided a-trous denoiser on frames in device memory (pt_denoise_device): the colour and its guide planes
+    (width*height*3 doubles each; albedo_ptr may be 0 without demodulate) into out_ptr (which may be rgb_ptr), with
+    denoise_workspace_doubles(width, height) doubles at work_ptr (16-byte aligned), queued on stream_ptr."""
+    _check(lib().pt_denoise_device(int(device), C.c_void_p(rgb_ptr or None), C.c_void_p(albedo_ptr or None),
+                                   C.c_void_p(normal_ptr or None), C.c_void_p(depth_ptr or None), int(width),
+                                   int(height), int(iterations), float(sigma_normal), float(sigma_depth),
+                                   float(sigma_colour), DENOISE_DEMODULATE if demodulate else 0,
+                                   C.c_void_p(out_ptr or None), C.c_void_p(work_ptr or None), C.c_void_p(stream_ptr)))
+
+
+def denoise(rgb: np.ndarray, albedo, normal: np.ndarray, depth: np.ndarray, width: int, height: int,
+            iterations: int = 5, sigma_normal: float = 0.5, sigma_depth: float = 0.1, sigma_colour: float = 0.0,
+            demodulate: bool = True, device: int = -1) -> np.ndarray:
+    """The guided a-trous denoiser on host arrays (pt_denoise): a frame and the planes render_aov gives for it,
+    (w*h, 3) float64 each (albedo may be None without demodulate); returns the (w*h, 3) denoised frame.  The colour
+    term is off at sigma_colour 0, the default."""
+    n = int(width) * int(height)
+    arrs = []
+    for a in (rgb, albedo, normal, depth):
+        if a is None:
+            arrs.append(None)
+            continue
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3)
+        if len(a) != n:
+            raise ValueError("each frame must hold width*height*3 doubles")
+        arrs.append(a)
+    out = np.zeros((n, 3), dtype=np.float64)
+    _check(lib().pt_denoise(int(device), *[None if a is None else _dptr(a) for a in arrs], int(width), int(height),
+                            int(iterations), float(sigma_normal), float(sigma_depth), float(sigma_colour),
+                            DENOISE_DEMODULATE if demodulate else 0, _dptr(out)))
+    return out
 
 
 def _image_args(rgba: np.ndarray, width: int, height: int):

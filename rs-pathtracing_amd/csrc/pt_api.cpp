@@ -21,6 +21,7 @@
 #include "../../include/rs_pathtracing.h"
 #include "pt_accel.hpp"
 #include "pt_aov.hpp"
+#include "pt_denoise.hpp"
 #include "pt_kernel.hpp"
 #include "pt_plan.hpp"
 #include "pt_scene.hpp"
@@ -1000,6 +1001,72 @@ int pt_encode_rgba8_device(int device, const double *d_rgb, size_t npix, uint8_t
     if (((uintptr_t)d_rgba & 3u) != 0) return fail(PT_ERR_INVALID, "rgba must be 4-byte aligned");
     if (device >= 0) HIP_TRY(hipSetDevice(device));
     HIP_TRY(launch_encode_rgba8(d_rgb, 0, npix, d_rgba, (hipStream_t)stream));
+    return PT_OK;
+}
+
+// ---- guided à-trous denoiser (pt_denoise.hpp): a pass over four frames, needs no renderer ----
+static_assert(PT_DENOISE_DEMODULATE == DENOISE_DEMODULATE && PT_DENOISE_MAX_ITERATIONS == DENOISE_MAX_ITERATIONS,
+              "the header states the denoiser's flag and iteration limit");
+namespace {
+// the checks the device form and the host form share (the pointers are device or host memory alike)
+int denoise_args_refused(const double *rgb, const double *albedo, const double *normal, const double *depth,
+                         uint32_t w, uint32_t h, uint32_t iterations, double sigma_normal, double sigma_depth,
+                         double sigma_colour, uint32_t flags, const double *out) {
+    if (!rgb || !normal || !depth || !out) return fail(PT_ERR_INVALID, "null argument");
+    if (flags & ~PT_DENOISE_DEMODULATE) return fail(PT_ERR_INVALID, "unknown denoise flag");
+    if ((flags & PT_DENOISE_DEMODULATE) && !albedo)
+        return fail(PT_ERR_INVALID, "PT_DENOISE_DEMODULATE needs the albedo plane");
+    if (w == 0 || h == 0) return fail(PT_ERR_INVALID, "width and height must be > 0");
+    if (iterations < 1 || iterations > PT_DENOISE_MAX_ITERATIONS)
+        return fail(PT_ERR_INVALID, "iterations must be 1.." + std::to_string(PT_DENOISE_MAX_ITERATIONS));
+    if (!(sigma_normal > 0.0) || !(sigma_depth > 0.0))
+        return fail(PT_ERR_INVALID, "sigma_normal and sigma_depth must be > 0");
+    if (!(sigma_colour >= 0.0)) return fail(PT_ERR_INVALID, "sigma_colour must be >= 0");
+    if (denoise_workspace_doubles(w, h) == 0 || (uint64_t)tiles_x_of(w) * tiles_y_of(h) > 0x7fffffffull)
+        return fail(PT_ERR_INVALID, "the frame is too large to denoise in one call");
+    return PT_OK;
+}
+}  // namespace
+
+size_t pt_denoise_workspace_doubles(uint32_t w, uint32_t h) { return denoise_workspace_doubles(w, h); }
+
+int pt_denoise_device(int device, const double *d_rgb, const double *d_albedo, const double *d_normal,
+                      const double *d_depth, uint32_t w, uint32_t h, uint32_t iterations, double sigma_normal,
+                      double sigma_depth, double sigma_colour, uint32_t flags, double *d_out, double *d_work,
+                      void *stream) {
+    if (int rc = denoise_args_refused(d_rgb, d_albedo, d_normal, d_depth, w, h, iterations, sigma_normal, sigma_depth,
+                                      sigma_colour, flags, d_out))
+        return rc;
+    if (!d_work) return fail(PT_ERR_INVALID, "null argument");
+    if (((uintptr_t)d_work & 15u) != 0) return fail(PT_ERR_INVALID, "the workspace must be 16-byte aligned");
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_denoise(d_rgb, d_albedo, d_normal, d_depth, w, h, iterations,
+                           denoise_consts(iterations, sigma_normal, sigma_depth, sigma_colour), flags, d_out, d_work,
+                           (hipStream_t)stream));
+    return PT_OK;
+}
+
+int pt_denoise(int device, const double *rgb, const double *albedo, const double *normal, const double *depth,
+               uint32_t w, uint32_t h, uint32_t iterations, double sigma_normal, double sigma_depth,
+               double sigma_colour, uint32_t flags, double *out) {
+    if (int rc = denoise_args_refused(rgb, albedo, normal, depth, w, h, iterations, sigma_normal, sigma_depth,
+                                      sigma_colour, flags, out))
+        return rc;
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    const size_t count = (size_t)w * h * 3;
+    const double *host[4] = {rgb, (flags & PT_DENOISE_DEMODULATE) ? albedo : nullptr, normal, depth};
+    DevBuf<double> dev[4], work;  // staging, freed on return; the frame is denoised in place in dev[0]
+    for (int k = 0; k < 4; k++)
+        if (host[k]) {
+            HIP_TRY(dev[k].alloc(count));
+            HIP_TRY(hipMemcpy(dev[k].p, host[k], count * sizeof(double), hipMemcpyHostToDevice));
+        }
+    HIP_TRY(work.alloc(denoise_workspace_doubles(w, h)));
+    if (int rc = pt_denoise_device(-1, dev[0].p, dev[1].p, dev[2].p, dev[3].p, w, h, iterations, sigma_normal,
+                                   sigma_depth, sigma_colour, flags, dev[0].p, work.p, nullptr))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpy(out, dev[0].p, count * sizeof(double), hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

@@ -4,7 +4,7 @@
 // (src/bin/main.rs:71-83, 281-289).  This does the same in one go, on the GPU:
 //
 //   pt_render scene.json [spp [w h]] [-d depth] [-s seed] [-o image.png|image.ppm] [-f frame.f64]
-//             [-c checkpoint -n window_spp [-x windows]] [-a prefix]
+//             [-c checkpoint -n window_spp [-x windows]] [-a prefix] [-D denoised.png]
 //
 // -o: the encoded image (PNG, or PPM by extension; default rendered.png, the name of the reference's "F" save).
 // -f: the linear f64 frame (w*h*3, row-major), for comparisons.
@@ -16,6 +16,10 @@
 //     prefix.albedo.png (the display encode), prefix.normal.png ((n + 1) / 2 per channel, linear, x 255.999) and
 //     prefix.depth.png (grey: mean t / coverage over the frame's largest such value; black where nothing is hit);
 //     with -f also the three raw planes, albedo then normal then depth, as prefix.aov.f64.
+// -D: the frame denoised on the device with its guide planes (pt_denoise_device at its defaults: 5 iterations,
+//     sigma_normal 0.5, sigma_depth 0.1, no colour term, demodulated), as a PNG through the display encode; with -f
+//     also the linear f64 frame as denoised.png.f64.  The planes are -a's when it was given, else they are rendered
+//     on the device for this.  -o and -f still get the noisy frame.  (-d is the depth, so the letter is a capital.)
 // Exit status: 0 done, 1 error (the library's message on stderr), 2 usage, 3 stopped with a checkpoint.
 #include <hip/hip_runtime_api.h>
 
@@ -36,7 +40,7 @@ namespace {
 int usage() {
     std::fprintf(stderr,
                  "usage: pt_render scene.json [spp [w h]] [-d depth] [-s seed] [-o image.png|.ppm] [-f frame.f64]\n"
-                 "                 [-c checkpoint -n window_spp [-x windows]] [-a aov_prefix]\n");
+                 "                 [-c checkpoint -n window_spp [-x windows]] [-a aov_prefix] [-D denoised.png]\n");
     return 2;
 }
 
@@ -82,7 +86,7 @@ int main(int argc, char **argv) {
     std::vector<const char *> pos;
     uint32_t depth = 50, window = 0, stop_after = 0;
     uint64_t seed = 1;
-    std::string out_img = "rendered.png", out_f64, ckpt, aov;
+    std::string out_img = "rendered.png", out_f64, ckpt, aov, denoised;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto val = [&](const char *name) -> const char * {
@@ -99,6 +103,7 @@ int main(int argc, char **argv) {
         else if (a == "-c") ckpt = val("-c");
         else if (a == "-n") window = (uint32_t)std::strtoul(val("-n"), nullptr, 10);
         else if (a == "-a") aov = val("-a");
+        else if (a == "-D") denoised = val("-D");
         else if (a == "-x") stop_after = (uint32_t)std::strtoul(val("-x"), nullptr, 10);
         else if (a.size() > 1 && a[0] == '-') return usage();
         else pos.push_back(argv[i]);
@@ -192,8 +197,9 @@ int main(int argc, char **argv) {
                                         : pt_write_png(out_img.c_str(), rgba.data(), w, h);
         if (rc) return fail(out_img.c_str(), rc);
     }
+    std::vector<double> planes;  // -a: albedo, normal, depth
     if (!aov.empty()) {
-        std::vector<double> planes(npix * 9);
+        planes.resize(npix * 9);
         double *alb = planes.data(), *nrm = alb + npix * 3, *dep = nrm + npix * 3;
         if ((rc = pt_render_aov(r, &cam, w, h, spp, seed, alb, nrm, dep))) return fail("guide planes", rc);
         if (!out_f64.empty() && !write_doubles(aov + ".aov.f64", planes)) return 1;
@@ -220,6 +226,40 @@ int main(int argc, char **argv) {
             rgba[i * 4 + 3] = 255;
         }
         if (save("depth")) return 1;
+    }
+    if (!denoised.empty()) {
+        // on the device: the frame, the three planes and the workspace in one allocation
+        const size_t plane = npix * 3, work = pt_denoise_workspace_doubles(w, h);
+        double *d = nullptr;
+        uint8_t *d_rgba = nullptr;
+        if (hipMalloc((void **)&d, (plane * 4 + work) * sizeof(double)) != hipSuccess ||
+            hipMalloc((void **)&d_rgba, npix * 4) != hipSuccess ||
+            hipMemcpy(d, rgb.data(), plane * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+            std::fprintf(stderr, "pt_render: no device memory for the denoiser\n");
+            return 1;
+        }
+        double *alb = d + plane, *nrm = alb + plane, *dep = nrm + plane;
+        if (!planes.empty()) {
+            if (hipMemcpy(alb, planes.data(), plane * 3 * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return 1;
+        } else if ((rc = pt_render_aov_device(r, &cam, w, h, spp, seed, 0, 1, alb, nrm, dep, nullptr))) {
+            return fail("guide planes", rc);
+        }
+        if ((rc = pt_denoise_device(-1, d, alb, nrm, dep, w, h, 5, 0.5, 0.1, 0.0, PT_DENOISE_DEMODULATE, d, dep + plane,
+                                    nullptr)))
+            return fail("denoise", rc);
+        if ((rc = pt_encode_rgba8_device(-1, d, npix, d_rgba, nullptr))) return fail("encode", rc);
+        std::vector<uint8_t> rgba(npix * 4);
+        std::vector<double> clean(plane);
+        if (hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(rgba.data(), d_rgba, rgba.size(), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(clean.data(), d, plane * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
+            std::fprintf(stderr, "pt_render: the denoiser failed on the device\n");
+            return 1;
+        }
+        (void)hipFree(d_rgba);
+        (void)hipFree(d);
+        if ((rc = pt_write_png(denoised.c_str(), rgba.data(), w, h))) return fail(denoised.c_str(), rc);
+        if (!out_f64.empty() && !write_doubles(denoised + ".f64", clean)) return 1;
     }
     std::printf("rendered %ux%u at %u spp, depth %u\n", w, h, spp, depth);
     pt_renderer_destroy(r);
