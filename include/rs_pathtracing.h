@@ -315,6 +315,60 @@ int pt_denoise(int device, const double *rgb, const double *albedo, const double
                uint32_t width, uint32_t height, uint32_t iterations, double sigma_normal, double sigma_depth,
                double sigma_colour, uint32_t flags, double *out);
 
+/* ---- per-pixel variance from sample windows, and the denoiser's variance term ---- */
+/* How far a frame is from converged, per pixel and channel: the variance of the
+ * pixel's mean (its square root is the standard error), estimated by batch
+ * means from the frame's own sample windows.  pt_render_device_samples leaves
+ * running sums in d_out between windows; pt_variance_window_device, run on
+ * d_out right after window `window` of `windows` (1-based; the first when 1,
+ * the last when it equals windows), differences them.  Window k covers samples
+ * [e_{k-1}, e_k), e_k = (uint64_t)k * samples_number / windows, n_k = e_k -
+ * e_{k-1}.  d_work holds pt_variance_workspace_doubles doubles (2 * count; the
+ * first window overwrites them, they need not be cleared) and must be kept
+ * between the windows of one frame; d_variance (count doubles, d_out's layout,
+ * the shard layout included; a padding element is 0) is written only by the
+ * last window, yet must be given on every call.  count is width*height*3 when
+ * world == 1, else pt_shard_tiles(...) * 768.  The arithmetic, step by step,
+ * is in rs-pathtracing_amd/csrc/pt_variance.hpp and DESIGN.md 3.9: f64, one
+ * fixed order, bit for bit the numpy restatement in tests/varianceref.py.
+ * pt_render_variance_device queues the whole frame: the windows through
+ * pt_render_device_samples, each followed by its accumulate launch, with no
+ * host synchronisation of its own; d_out ends bit-identical to
+ * pt_render_device's.  pt_denoise_variance_device is pt_denoise_device with,
+ * in place of the colour term, a luminance weight scaled by each pixel's own
+ * variance (d_variance: the plane above, of a whole frame), so it backs off
+ * where the frame has converged; sigma_variance (8 is the recommended default)
+ * = +inf weighs 1 and gives pt_denoise_device's frame at sigma_colour 0 bit
+ * for bit.  Same workspace as pt_denoise_device.  PT_ERR_INVALID, the call
+ * writing nothing: a NULL pointer (d_albedo alone may be NULL without
+ * PT_DENOISE_DEMODULATE), a zero size, windows < 2 or > samples_number, window
+ * outside 1..windows, n_k outside 1..samples_number, rank >= world (or a rank
+ * that holds no tile), sigma_variance not greater than 0 or NaN, and
+ * pt_denoise_device's cases.  PT_ERR_STATE while a pt_render_start frame is
+ * in flight.  The accumulation state is not checkpointed.  (Library 0.4.3; no
+ * ABI change.) */
+/* 2 * count; 0 on a zero size or rank >= world */
+size_t pt_variance_workspace_doubles(uint32_t width, uint32_t height, uint32_t rank, uint32_t world);
+int pt_variance_window_device(int device, const double *d_out, size_t count, uint32_t n_k, uint32_t samples_number,
+                              uint32_t window, uint32_t windows, double *d_work, double *d_variance,
+                              void *hip_stream);
+int pt_render_variance_device(pt_renderer *r, const pt_camera *camera, uint32_t width, uint32_t height,
+                              uint32_t samples_number, uint64_t seed, uint32_t rank, uint32_t world,
+                              uint32_t windows, double *d_out, double *d_variance, double *d_work,
+                              void *hip_stream);
+/* the same into host buffers (world 1); allocates, copies, blocks */
+int pt_render_variance(pt_renderer *r, const pt_camera *camera, uint32_t width, uint32_t height,
+                       uint32_t samples_number, uint64_t seed, uint32_t windows, double *rgb, double *variance);
+int pt_denoise_variance_device(int device, const double *d_rgb, const double *d_albedo, const double *d_normal,
+                               const double *d_depth, const double *d_variance, uint32_t width, uint32_t height,
+                               uint32_t iterations, double sigma_normal, double sigma_depth, double sigma_variance,
+                               uint32_t flags, double *d_out, double *d_work, void *hip_stream);
+/* the same from and to host buffers; allocates, copies, blocks */
+int pt_denoise_variance(int device, const double *rgb, const double *albedo, const double *normal,
+                        const double *depth, const double *variance, uint32_t width, uint32_t height,
+                        uint32_t iterations, double sigma_normal, double sigma_depth, double sigma_variance,
+                        uint32_t flags, double *out);
+
 /* ---- resumable frames (checkpoint / resume) ----------------------------- */
 /* The reference renders a frame in one go and keeps nothing between runs
  * (Renderer::render, src/renderer/mod.rs:67-114; its GUI saves only the

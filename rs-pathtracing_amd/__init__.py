@@ -52,6 +52,8 @@ EXPORTS = [
     "pt_render_device_samples", "pt_checkpoint_save", "pt_checkpoint_load",
     "pt_render_aov_device", "pt_render_aov",
     "pt_denoise_workspace_doubles", "pt_denoise_device", "pt_denoise",
+    "pt_variance_workspace_doubles", "pt_variance_window_device", "pt_render_variance_device", "pt_render_variance",
+    "pt_denoise_variance_device", "pt_denoise_variance",
 ]
 DENOISE_DEMODULATE = 1  # PT_DENOISE_DEMODULATE
 DENOISE_MAX_ITERATIONS = 8  # PT_DENOISE_MAX_ITERATIONS
@@ -164,6 +166,15 @@ def lib():
         "pt_denoise_device": (C.c_int, [C.c_int, vp, vp, vp, vp, u32, u32, u32, C.c_double, C.c_double, C.c_double,
                                         u32, vp, vp, vp]),
         "pt_denoise": (C.c_int, [C.c_int, d, d, d, d, u32, u32, u32, C.c_double, C.c_double, C.c_double, u32, d]),
+        "pt_variance_workspace_doubles": (sz, [u32, u32, u32, u32]),
+        "pt_variance_window_device": (C.c_int, [C.c_int, vp, sz, u32, u32, u32, u32, vp, vp, vp]),
+        "pt_render_variance_device": (C.c_int, [vp, C.POINTER(CameraStruct), u32, u32, u32, u64, u32, u32, u32, vp, vp,
+                                                vp, vp]),
+        "pt_render_variance": (C.c_int, [vp, C.POINTER(CameraStruct), u32, u32, u32, u64, u32, d, d]),
+        "pt_denoise_variance_device": (C.c_int, [C.c_int, vp, vp, vp, vp, vp, u32, u32, u32, C.c_double, C.c_double,
+                                                 C.c_double, u32, vp, vp, vp]),
+        "pt_denoise_variance": (C.c_int, [C.c_int, d, d, d, d, d, u32, u32, u32, C.c_double, C.c_double, C.c_double,
+                                          u32, d]),
         "pt_checkpoint_save": (C.c_int, [C.c_char_p, C.POINTER(CheckpointStruct), d]),
         "pt_checkpoint_load": (C.c_int, [C.c_char_p, C.POINTER(CheckpointStruct), d, u64]),
         "pt_shard_tiles": (u32, [u32, u32, u32, u32]),
@@ -462,6 +473,30 @@ class HipRenderer(Renderer):
                                           C.c_void_p(albedo_ptr or None), C.c_void_p(normal_ptr or None),
                                           C.c_void_p(depth_ptr or None), C.c_void_p(stream_ptr)))
 
+    # ---- per-pixel variance from sample windows (pt_render_variance) ----
+    def render_variance(self, camera: Camera, img_params: ImageParams, samples_number: int, seed=None, windows: int = 8):
+        """(rgb, variance): the frame render(camera, img_params, samples_number, seed) renders, bit for bit, and
+        the variance of each pixel's mean per channel ((w*h, 3) float64 each; its square root is the standard
+        error), estimated from `windows` sample windows of the frame (2 <= windows <= samples_number).  See
+        pt_render_variance."""
+        s = self.seed if seed is None else int(seed)
+        n = img_params.width * img_params.height
+        rgb, var = np.zeros((n, 3), dtype=np.float64), np.zeros((n, 3), dtype=np.float64)
+        _check(lib().pt_render_variance(self._h, C.byref(camera._c), img_params.width, img_params.height,
+                                        int(samples_number), s, int(windows), _dptr(rgb), _dptr(var)))
+        return rgb, var
+
+    def render_variance_device(self, camera: Camera, width: int, height: int, spp: int, seed: int, rank: int,
+                               world: int, windows: int, out_ptr: int, variance_ptr: int, work_ptr: int,
+                               stream_ptr: int = 0):
+        """render_device in `windows` sample windows, with the variance of each element's mean into variance_ptr
+        (out_ptr's layout) and variance_workspace_doubles(width, height, rank, world) doubles at work_ptr, all
+        queued on stream_ptr (pt_render_variance_device)."""
+        _check(lib().pt_render_variance_device(self._h, C.byref(camera._c), width, height, spp, seed, rank, world,
+                                               int(windows), C.c_void_p(out_ptr or None),
+                                               C.c_void_p(variance_ptr or None), C.c_void_p(work_ptr or None),
+                                               C.c_void_p(stream_ptr)))
+
     # ---- probes --------------------------------------------------------
     def closest_hit(self, rays: np.ndarray, min_t: float = 0.001, max_t: float = float("inf")) -> np.ndarray:
         rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
@@ -676,6 +711,62 @@ def denoise(rgb: np.ndarray, albedo, normal: np.ndarray, depth: np.ndarray, widt
     _check(lib().pt_denoise(int(device), *[None if a is None else _dptr(a) for a in arrs], int(width), int(height),
                             int(iterations), float(sigma_normal), float(sigma_depth), float(sigma_colour),
                             DENOISE_DEMODULATE if demodulate else 0, _dptr(out)))
+    return out
+
+
+def variance_workspace_doubles(width: int, height: int, rank: int = 0, world: int = 1) -> int:
+    """Doubles of device workspace the variance accumulation needs for one rank's d_out: 2 per element
+    (pt_variance_workspace_doubles)."""
+    return int(lib().pt_variance_workspace_doubles(int(width), int(height), int(rank), int(world)))
+
+
+def variance_window_device(out_ptr: int, count: int, n_k: int, samples_number: int, window: int, windows: int,
+                           work_ptr: int, variance_ptr: int, stream_ptr: int = 0, device: int = -1):
+    """The accumulation step after window `window` of `windows` (1-based) of a frame rendered with
+    render_device_samples: out_ptr holds the running sums (the means after the last window), n_k is the window's
+    sample count; variance_ptr is written by the last window only (pt_variance_window_device)."""
+    _check(lib().pt_variance_window_device(int(device), C.c_void_p(out_ptr or None), int(count), int(n_k),
+                                           int(samples_number), int(window), int(windows),
+                                           C.c_void_p(work_ptr or None), C.c_void_p(variance_ptr or None),
+                                           C.c_void_p(stream_ptr)))
+
+
+def denoise_variance_device(rgb_ptr: int, albedo_ptr: int, normal_ptr: int, depth_ptr: int, variance_ptr: int,
+                            width: int, height: int, out_ptr: int, work_ptr: int, iterations: int = 5,
+                            sigma_normal: float = 0.5, sigma_depth: float = 0.1, sigma_variance: float = 8.0,
+                            demodulate: bool = True, stream_ptr: int = 0, device: int = -1):
+    """denoise_device with the variance term: variance_ptr is the frame's variance plane (render_variance_device,
+    world 1), and a luminance weight scaled by each pixel's own variance replaces the colour term
+    (pt_denoise_variance_device).  The same workspace as denoise_device."""
+    _check(lib().pt_denoise_variance_device(int(device), C.c_void_p(rgb_ptr or None), C.c_void_p(albedo_ptr or None),
+                                            C.c_void_p(normal_ptr or None), C.c_void_p(depth_ptr or None),
+                                            C.c_void_p(variance_ptr or None), int(width), int(height),
+                                            int(iterations), float(sigma_normal), float(sigma_depth),
+                                            float(sigma_variance), DENOISE_DEMODULATE if demodulate else 0,
+                                            C.c_void_p(out_ptr or None), C.c_void_p(work_ptr or None),
+                                            C.c_void_p(stream_ptr)))
+
+
+def denoise_variance(rgb: np.ndarray, albedo, normal: np.ndarray, depth: np.ndarray, variance: np.ndarray,
+                     width: int, height: int, iterations: int = 5, sigma_normal: float = 0.5,
+                     sigma_depth: float = 0.1, sigma_variance: float = 8.0, demodulate: bool = True,
+                     device: int = -1) -> np.ndarray:
+    """denoise with the variance term on host arrays (pt_denoise_variance): the frame and the variance plane
+    render_variance gives, and the planes render_aov gives for it; returns the (w*h, 3) denoised frame."""
+    n = int(width) * int(height)
+    arrs = []
+    for a in (rgb, albedo, normal, depth, variance):
+        if a is None:
+            arrs.append(None)
+            continue
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3)
+        if len(a) != n:
+            raise ValueError("each frame must hold width*height*3 doubles")
+        arrs.append(a)
+    out = np.zeros((n, 3), dtype=np.float64)
+    _check(lib().pt_denoise_variance(int(device), *[None if a is None else _dptr(a) for a in arrs], int(width),
+                                     int(height), int(iterations), float(sigma_normal), float(sigma_depth),
+                                     float(sigma_variance), DENOISE_DEMODULATE if demodulate else 0, _dptr(out)))
     return out
 
 

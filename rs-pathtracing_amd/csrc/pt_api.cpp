@@ -25,6 +25,7 @@
 #include "pt_kernel.hpp"
 #include "pt_plan.hpp"
 #include "pt_scene.hpp"
+#include "pt_variance.hpp"
 
 using namespace pt;
 
@@ -1064,6 +1065,133 @@ int pt_denoise(int device, const double *rgb, const double *albedo, const double
     HIP_TRY(work.alloc(denoise_workspace_doubles(w, h)));
     if (int rc = pt_denoise_device(-1, dev[0].p, dev[1].p, dev[2].p, dev[3].p, w, h, iterations, sigma_normal,
                                    sigma_depth, sigma_colour, flags, dev[0].p, work.p, nullptr))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpy(out, dev[0].p, count * sizeof(double), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// ---- per-pixel variance from sample windows (pt_variance.hpp) and the denoiser's variance term ----
+namespace {
+// elements of one rank's d_out; 0 on a zero size, rank >= world, or a count whose workspace does not fit
+uint64_t variance_count(uint32_t w, uint32_t h, uint32_t rank, uint32_t world) {
+    if (w == 0 || h == 0 || world == 0 || rank >= world) return 0;
+    const uint64_t count = world == 1 ? (uint64_t)w * h * 3 : (uint64_t)pt_shard_tiles(w, h, rank, world) * 768;
+    return variance_workspace_doubles(count) ? count : 0;
+}
+
+int variance_window_refused(const double *d_out, size_t count, uint32_t n_k, uint32_t spp, uint32_t window,
+                            uint32_t windows, const double *d_work, const double *d_variance) {
+    if (!d_out || !d_work || !d_variance) return fail(PT_ERR_INVALID, "null argument");
+    if (count == 0 || variance_workspace_doubles(count) == 0 || (count + 255) / 256 > 0x7fffffffull)
+        return fail(PT_ERR_INVALID, "count must be > 0 and fit one launch");
+    if (windows < 2 || windows > spp) return fail(PT_ERR_INVALID, "windows must be 2..samples_number");
+    if (window < 1 || window > windows) return fail(PT_ERR_INVALID, "window must be 1..windows");
+    if (n_k < 1 || n_k > spp) return fail(PT_ERR_INVALID, "n_k must be 1..samples_number");
+    return PT_OK;
+}
+
+int denoise_variance_refused(const double *rgb, const double *albedo, const double *normal, const double *depth,
+                             const double *variance, uint32_t w, uint32_t h, uint32_t iterations, double sigma_normal,
+                             double sigma_depth, double sigma_variance, uint32_t flags, const double *out) {
+    if (!variance) return fail(PT_ERR_INVALID, "null argument");
+    if (!(sigma_variance > 0.0)) return fail(PT_ERR_INVALID, "sigma_variance must be > 0");
+    return denoise_args_refused(rgb, albedo, normal, depth, w, h, iterations, sigma_normal, sigma_depth, 0.0, flags,
+                                out);
+}
+}  // namespace
+
+size_t pt_variance_workspace_doubles(uint32_t w, uint32_t h, uint32_t rank, uint32_t world) {
+    return variance_workspace_doubles(variance_count(w, h, rank, world));
+}
+
+int pt_variance_window_device(int device, const double *d_out, size_t count, uint32_t n_k, uint32_t spp,
+                              uint32_t window, uint32_t windows, double *d_work, double *d_variance, void *stream) {
+    if (int rc = variance_window_refused(d_out, count, n_k, spp, window, windows, d_work, d_variance)) return rc;
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_variance_window(d_out, count, variance_consts(n_k, spp, windows), window == 1, window == windows,
+                                   d_work, d_variance, (hipStream_t)stream));
+    return PT_OK;
+}
+
+int pt_render_variance_device(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                              uint64_t seed, uint32_t rank, uint32_t world, uint32_t windows, double *d_out,
+                              double *d_variance, double *d_work, void *stream) {
+    if (!r || !cam || !d_out || !d_variance || !d_work) return fail(PT_ERR_INVALID, "null argument");
+    if (w == 0 || h == 0 || spp == 0) return fail(PT_ERR_INVALID, "width, height and samples_number must be > 0");
+    if (world == 0 || rank >= world) return fail(PT_ERR_INVALID, "rank must be < world");
+    if (windows < 2 || windows > spp) return fail(PT_ERR_INVALID, "windows must be 2..samples_number");
+    const uint64_t count = variance_count(w, h, rank, world);
+    if (count == 0 || (count + 255) / 256 > 0x7fffffffull)
+        return fail(PT_ERR_INVALID, "the frame is too large for the variance pass (or the rank has no tile)");
+    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
+    // the frame's own windows, each followed by its accumulate launch on the same stream: no sync of ours
+    for (uint32_t k = 1; k <= windows; k++) {
+        const uint32_t e0 = variance_edge(k - 1, spp, windows), e1 = variance_edge(k, spp, windows);
+        if (int rc = pt_render_device_samples(r, cam, w, h, spp, seed, rank, world, e0, e1, d_out, stream)) return rc;
+        if (int rc = pt_variance_window_device(-1, d_out, (size_t)count, e1 - e0, spp, k, windows, d_work, d_variance,
+                                               stream))
+            return rc;
+    }
+    return PT_OK;
+}
+
+int pt_render_variance(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
+                       uint32_t windows, double *rgb, double *variance) {
+    if (!r || !cam || !rgb || !variance) return fail(PT_ERR_INVALID, "null argument");
+    if (w == 0 || h == 0 || spp == 0) return fail(PT_ERR_INVALID, "width, height and samples_number must be > 0");
+    if (windows < 2 || windows > spp) return fail(PT_ERR_INVALID, "windows must be 2..samples_number");
+    const uint64_t count = variance_count(w, h, 0, 1);
+    if (count == 0) return fail(PT_ERR_INVALID, "the frame is too large for the variance pass");
+    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
+    HIP_TRY(hipSetDevice(r->device()));
+    DevBuf<double> out, var, work;  // staging, freed on return
+    HIP_TRY(out.alloc((size_t)count));
+    HIP_TRY(var.alloc((size_t)count));
+    HIP_TRY(work.alloc(variance_workspace_doubles(count)));
+    if (int rc = pt_render_variance_device(r, cam, w, h, spp, seed, 0, 1, windows, out.p, var.p, work.p, r->stream()))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(r->stream()));
+    HIP_TRY(hipMemcpy(rgb, out.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(variance, var.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_denoise_variance_device(int device, const double *d_rgb, const double *d_albedo, const double *d_normal,
+                               const double *d_depth, const double *d_variance, uint32_t w, uint32_t h,
+                               uint32_t iterations, double sigma_normal, double sigma_depth, double sigma_variance,
+                               uint32_t flags, double *d_out, double *d_work, void *stream) {
+    if (int rc = denoise_variance_refused(d_rgb, d_albedo, d_normal, d_depth, d_variance, w, h, iterations,
+                                          sigma_normal, sigma_depth, sigma_variance, flags, d_out))
+        return rc;
+    if (!d_work) return fail(PT_ERR_INVALID, "null argument");
+    if (((uintptr_t)d_work & 15u) != 0) return fail(PT_ERR_INVALID, "the workspace must be 16-byte aligned");
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_denoise_variance(d_rgb, d_albedo, d_normal, d_depth, d_variance, w, h, iterations,
+                                    denoise_consts(iterations, sigma_normal, sigma_depth, 0.0),
+                                    denoise_variance_rv(sigma_variance), flags, d_out, d_work, (hipStream_t)stream));
+    return PT_OK;
+}
+
+int pt_denoise_variance(int device, const double *rgb, const double *albedo, const double *normal,
+                        const double *depth, const double *variance, uint32_t w, uint32_t h, uint32_t iterations,
+                        double sigma_normal, double sigma_depth, double sigma_variance, uint32_t flags, double *out) {
+    if (int rc = denoise_variance_refused(rgb, albedo, normal, depth, variance, w, h, iterations, sigma_normal,
+                                          sigma_depth, sigma_variance, flags, out))
+        return rc;
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    const size_t count = (size_t)w * h * 3;
+    const double *host[5] = {rgb, (flags & PT_DENOISE_DEMODULATE) ? albedo : nullptr, normal, depth, variance};
+    DevBuf<double> dev[5], work;  // staging, freed on return; the frame is denoised in place in dev[0]
+    for (int k = 0; k < 5; k++)
+        if (host[k]) {
+            HIP_TRY(dev[k].alloc(count));
+            HIP_TRY(hipMemcpy(dev[k].p, host[k], count * sizeof(double), hipMemcpyHostToDevice));
+        }
+    HIP_TRY(work.alloc(denoise_workspace_doubles(w, h)));
+    if (int rc = pt_denoise_variance_device(-1, dev[0].p, dev[1].p, dev[2].p, dev[3].p, dev[4].p, w, h, iterations,
+                                            sigma_normal, sigma_depth, sigma_variance, flags, dev[0].p, work.p,
+                                            nullptr))
         return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     HIP_TRY(hipMemcpy(out, dev[0].p, count * sizeof(double), hipMemcpyDeviceToHost));

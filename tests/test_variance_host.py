@@ -1,0 +1,368 @@
+"""The variance estimate and the denoiser's variance term on the CPU: the per-element function of
+rs-pathtracing_amd/csrc/pt_variance.hpp and the per-pixel functions of pt_denoise.hpp (the ones the variance_window,
+denoise_records_variance and denoise_tiles_variance kernels run per lane), compiled for the host by
+tests/native/variance.mk, against the numpy restatement tests/varianceref.py, bit for bit; the identity with the plain
+denoiser; the filter's quality and the estimate's size against converged oracle frames; and the argument checks of the
+new exports, which return before any HIP call.  tests/test_gpu_variance.py repeats the comparisons with the same code
+compiled for gfx950."""
+import ctypes as C
+import functools
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import aovref
+import denoiseref
+import varianceref
+from conftest import native_lib
+
+NATIVE = Path(__file__).resolve().parent / "native"
+GOLDEN = Path(__file__).resolve().parent / "golden"
+INF = float("inf")
+NAN = float("nan")
+d = C.POINTER(C.c_double)
+
+
+@pytest.fixture(scope="module")
+def V():
+    subprocess.run(["make", "-s", "-C", str(NATIVE), "-f", "variance.mk"], check=True)
+    L = C.CDLL(native_lib("libvariance.so"))
+    L.vr_window.restype = C.c_size_t
+    L.vr_window.argtypes = [d, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, d, d]
+    L.vr_edge.restype = C.c_uint32
+    L.vr_edge.argtypes = [C.c_uint32] * 3
+    L.vr_denoise.restype = C.c_size_t
+    L.vr_denoise.argtypes = [d, d, d, d, d, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double,
+                             C.c_uint32, d]
+    return L
+
+
+def host_variance(V, snaps, n):
+    """The K windows through the host build, the workspace starting as garbage; the plane is written by the last
+    window alone."""
+    k, count = len(snaps), snaps[0].size
+    e = varianceref.edges(n, k)
+    work = np.full(2 * count, np.nan)
+    var = np.full(count, -7.25)
+    for j in range(1, k + 1):
+        out = np.ascontiguousarray(snaps[j - 1], dtype=np.float64)
+        assert np.all(var == -7.25)
+        assert V.vr_window(out.ctypes.data_as(d), count, e[j] - e[j - 1], n, j, k, work.ctypes.data_as(d),
+                           var.ctypes.data_as(d)) == 2 * count
+    return var
+
+
+def same_flat(got, ref):
+    assert np.all(np.isfinite(got))
+    bad = np.flatnonzero(got != ref)
+    assert bad.size == 0, "%d of %d elements differ (first %s)" % (bad.size, ref.size, bad[:8].tolist())
+
+
+def same(got, ref):
+    assert np.all(np.isfinite(got))
+    bad = np.flatnonzero(np.any(got != ref, axis=1))
+    assert bad.size == 0, "%d of %d pixels differ (first %s)" % (bad.size, len(ref), bad[:8].tolist())
+
+
+# ---- the accumulation, bit for bit against the restatement ----
+
+def test_window_edges(V):
+    assert varianceref.edges(7, 3) == [0, 2, 4, 7]
+    for n, k in varianceref.PLANS + [(4096, 7)]:
+        e = [V.vr_edge(j, n, k) for j in range(k + 1)]
+        assert e == varianceref.edges(n, k)
+        assert all(b > a for a, b in zip(e, e[1:]))  # no window is empty
+    n, k = 0xFFFFFFFF, 0xFFFFFFFE  # the product k * N is taken in 64 bits
+    assert [V.vr_edge(j, n, k) for j in (0, 1, k - 1, k)] == [0, 1, (k - 1) * n // k, n]
+
+
+@pytest.mark.parametrize("n,k", varianceref.PLANS)
+def test_synthetic_sums_equal_the_restatement(V, n, k):
+    count = 40 * 24 * 3
+    snaps = varianceref.synthetic(count, n, k)
+    ref, m2 = varianceref.variance(snaps, n, return_m2=True)
+    same_flat(host_variance(V, snaps, n), ref)
+    # the inputs hold what they are for: m2 rounded below 0 and clamped, zero sums, both magnitudes, real noise
+    if n > 2:
+        assert np.sum(m2 < 0.0) >= 5
+    assert np.all(ref >= 0.0) and np.sum(ref[m2 < 0.0] != 0.0) == 0
+    assert np.sum(snaps[-1] == 0.0) >= 50 and np.sum(snaps[-1] > 1e148) >= 10
+    assert np.sum((snaps[-1] > 0.0) & (snaps[-1] < 1e-148)) >= 10 and np.sum(ref > 1e-3) >= 1000
+
+
+@pytest.mark.parametrize("cw,ch", [(20, 13), (17, 1), (1, 1)])
+def test_small_shapes(V, cw, ch):
+    for n, k in varianceref.PLANS:
+        snaps = varianceref.synthetic(cw * ch * 3, n, k)
+        same_flat(host_variance(V, snaps, n), varianceref.variance(snaps, n))
+
+
+def test_shard_count_with_padding(V):
+    """40x24 is 3x2 tiles; each of 3 ranks holds 2 tiles of 256 pixels, the lower row's tiles with 8 of 16 rows in
+    the frame: the elements past the frame are 0 in every snapshot and get variance 0."""
+    count, padding = 2 * 768, 128 * 3
+    snaps = varianceref.synthetic(count, 7, 3, padding=padding)
+    got = host_variance(V, snaps, 7)
+    same_flat(got, varianceref.variance(snaps, 7))
+    assert np.all(got[-padding:] == 0.0) and np.any(got[:-padding] > 0.0)
+
+
+def test_the_estimate_is_the_batch_means_variance():
+    """Against the textbook form in plain numpy, within rounding: equal windows, sum (mean_k - mean)^2 / (K (K-1))."""
+    n, k, count = 64, 8, 2000
+    g = np.random.default_rng(5)
+    x = g.random((n, count))
+    cum = np.cumsum(x, axis=0)
+    snaps = [cum[(j + 1) * 8 - 1] for j in range(k)]
+    snaps[-1] = snaps[-1] / n
+    means = x.reshape(k, 8, count).mean(axis=1)
+    textbook = means.var(axis=0, ddof=1) / k
+    assert np.allclose(varianceref.variance(snaps, n), textbook, rtol=1e-9, atol=0.0)
+
+
+# ---- the denoiser's variance term, bit for bit against the restatement ----
+
+def host_denoise(V, rgb, albedo, normal, depth, var, w, h, iterations=5, sigma_normal=0.5, sigma_depth=0.1,
+                 sigma_variance=8.0, demodulate=True):
+    arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (rgb, albedo, normal, depth, var)]
+    out = np.full((w * h, 3), -7.25)
+    used = V.vr_denoise(*[None if a is None else a.ctypes.data_as(d) for a in arrs], w, h, iterations, sigma_normal,
+                        sigma_depth, sigma_variance, 1 if demodulate else 0, out.ctypes.data_as(d))
+    assert used == w * h * 12
+    return out
+
+
+SETTINGS = {
+    "defaults": {},
+    "one_iteration": dict(iterations=1),
+    "eight_iterations": dict(iterations=8),
+    "no_demodulation": dict(demodulate=False),
+    "sigma_variance_1": dict(sigma_variance=1.0),
+}
+
+
+def random_case(w=40, h=24):
+    return denoiseref.random_planes(w, h) + (varianceref.random_variance(w, h),)
+
+
+@pytest.mark.parametrize("setting", list(SETTINGS))
+def test_random_planes_equal_the_restatement(V, setting):
+    w, h = 40, 24
+    fr = random_case(w, h)
+    assert np.sum(np.all(fr[4] == 0.0, axis=1)) >= 100 and np.sum(fr[4] > 0.0) >= 1500
+    kw = SETTINGS[setting]
+    got = host_denoise(V, *fr, w, h, **kw)
+    ref = varianceref.denoise_variance(*fr, w, h, **kw)
+    same(got, ref)
+    plain = {k: v for k, v in kw.items() if k != "sigma_variance"}
+    assert np.any(got != denoiseref.denoise(*fr[:4], w, h, **plain))  # the term is not a no-op
+    if setting == "no_demodulation":
+        same(host_denoise(V, fr[0], None, *fr[2:], w, h, **kw), ref)  # the albedo is not read
+
+
+def crop(fr, w, cw, ch):
+    return tuple(np.ascontiguousarray(a.reshape(-1, w, 3)[:ch, :cw]).reshape(cw * ch, 3) for a in fr)
+
+
+@pytest.mark.parametrize("cw,ch", [(20, 13), (17, 1), (1, 1)])
+def test_small_shapes_of_the_denoiser(V, cw, ch):
+    fr = crop(random_case(), 40, cw, ch)
+    same(host_denoise(V, *fr, cw, ch), varianceref.denoise_variance(*fr, cw, ch))
+    same(host_denoise(V, *fr, cw, ch, iterations=8, sigma_variance=1.0),
+         varianceref.denoise_variance(*fr, cw, ch, iterations=8, sigma_variance=1.0))
+
+
+def test_in_place(V):
+    w, h = 40, 24
+    fr = random_case(w, h)
+    buf = fr[0].copy()
+    p = [a.ctypes.data_as(d) for a in (buf, *[np.ascontiguousarray(a) for a in fr[1:]])]
+    V.vr_denoise(*p, w, h, 5, 0.5, 0.1, 8.0, 1, p[0])
+    same(buf, varianceref.denoise_variance(*fr, w, h))
+
+
+def test_all_zero_variance_plane(V):
+    """g = 0 everywhere: rl = rv / 1e-10, every tap of another luminance weighs 0 and the centre tap 9/64, so the
+    output is finite (and close to the input)."""
+    w, h = 40, 24
+    fr = denoiseref.random_planes(w, h) + (np.zeros((w * h, 3)),)
+    got = host_denoise(V, *fr, w, h)
+    same(got, varianceref.denoise_variance(*fr, w, h))
+    assert np.allclose(got, fr[0], rtol=1e-12, atol=0.0)
+
+
+@pytest.mark.parametrize("setting", ["defaults", "no_demodulation", "eight_iterations"])
+def test_infinite_sigma_variance_is_the_plain_denoiser(V, setting):
+    """rv = 0: xl = 0 and f(xl) = 1 for every tap, so the frame equals denoiseref.denoise's (sigma_colour 0) bit
+    for bit."""
+    w, h = 40, 24
+    fr = random_case(w, h)
+    kw = SETTINGS[setting]
+    plain = denoiseref.denoise(*fr[:4], w, h, **kw)
+    same(host_denoise(V, *fr, w, h, sigma_variance=INF, **kw), plain)
+    same(varianceref.denoise_variance(*fr, w, h, sigma_variance=INF, **kw), plain)
+
+
+# ---- quality and the size of the estimate, against converged oracle frames ----
+
+@functools.lru_cache(maxsize=None)
+def windowed(name, spp, windows):
+    """(w, h, frame, variance plane, guide planes, converged frame) of an aovref case at `spp` samples (frame seed 3,
+    depth 8) from the oracle.  The oracle has no sample windows, but its frame of e samples is the mean of the first
+    e samples of any longer frame (the sample keys are per sample index), so the running sums after window k are
+    restated as render(e_k) * e_k: a product of a rounded mean, not the GPU's exact sums (those are tested on the
+    GPU)."""
+    _, _, w, h, _, osc, _ = aovref.case(name)
+    e = varianceref.edges(spp, windows)
+    snaps = [osc.render(w, h, e[j], 8, aovref.FRAME_SEED) for j in range(1, windows + 1)]
+    frame = snaps[-1]
+    sums = [s * np.float64(e[j + 1]) for j, s in enumerate(snaps[:-1])] + [frame]
+    var = varianceref.variance(sums, spp)
+    planes = aovref.planes(osc, w, h, spp, aovref.FRAME_SEED)
+    ref = np.load(GOLDEN / ("denoise_cornell_ref.npy" if name == "cornell" else "variance_spheres_ref.npy"))
+    assert ref.shape == (w * h, 3)
+    return w, h, frame, var, planes, ref
+
+
+def ratios(name, spp, windows, sigma_variance=8.0, sigma_colour=4.0):
+    w, h, frame, var, pl, ref = windowed(name, spp, windows)
+    fr = (frame, pl["albedo"], pl["normal"], pl["depth"])
+    before = denoiseref.rms(frame, ref)
+    guided = varianceref.denoise_variance(*fr, var, w, h, sigma_variance=sigma_variance)
+    out = dict(
+        guides=denoiseref.rms(denoiseref.denoise(*fr, w, h), ref) / before,
+        colour=denoiseref.rms(denoiseref.denoise(*fr, w, h, sigma_colour=sigma_colour), ref) / before,
+        variance=denoiseref.rms(guided, ref) / before)
+    print("%s %d spp / %d windows: noisy rms %.4f; guides only %.3f, colour term %.3f, variance term (sigma %g) %.3f"
+          % (name, spp, windows, before, out["guides"], out["colour"], sigma_variance, out["variance"]))
+    return out
+
+
+@pytest.mark.parametrize("name", ["cornell", "spheres"])
+def test_variance_term_beats_guides_only_at_64_spp(name):
+    """64 spp in 8 windows, RMS against the converged frame over the noisy frame's: the variance term at its default
+    sigma 8 is better than the guides alone (which on spheres make the frame worse than leaving it)."""
+    r = ratios(name, 64, 8)
+    assert r["variance"] < r["guides"]
+
+
+def test_variance_term_beats_the_fixed_colour_term_at_4_spp():
+    """cornell, 4 spp in 4 windows: the variance term is better than the fixed colour term at sigma 4, which keeps
+    the fireflies.  (The guides alone are better still there: 4 batches of 1 sample estimate the variance poorly;
+    DESIGN.md 3.9 has the table.)"""
+    r = ratios("cornell", 4, 4)
+    assert r["variance"] < r["colour"]
+
+
+@pytest.mark.parametrize("name", ["cornell", "spheres"])
+def test_the_estimate_is_the_size_of_the_true_error(name):
+    """The RMS of the standard error of the luminance (sqrt of the luminance variance) is within a factor of 2 of the
+    true RMS luminance error at 64 spp / 8 windows.  (Loose: cornell's small light makes its noise heavy-tailed.)"""
+    w, h, frame, var, _, ref = windowed(name, 64, 8)
+    true = float(np.sqrt(np.mean((varianceref.luminance(frame) - varianceref.luminance(ref)) ** 2)))
+    est = float(np.sqrt(np.mean(varianceref.luminance_variance(var))))
+    print("%s: true rms luminance error %.5f, estimate %.5f (%.2fx)" % (name, true, est, est / true))
+    assert 0.5 < est / true < 2.0
+
+
+# ---- the C-ABI: exports and argument errors (no HIP call is made) ----
+
+NAMES = ("pt_variance_workspace_doubles", "pt_variance_window_device", "pt_render_variance_device",
+         "pt_render_variance", "pt_denoise_variance_device", "pt_denoise_variance")
+
+
+def test_exports(pt):
+    L = C.CDLL(str(pt.LIB_PATH))
+    for name in NAMES:
+        assert name in pt.EXPORTS and hasattr(L, name)
+    assert pt.variance_workspace_doubles(40, 24) == 40 * 24 * 3 * 2
+    assert pt.variance_workspace_doubles(40, 24, 1, 3) == 2 * 768 * 2  # 6 tiles over 3 ranks
+    assert pt.variance_workspace_doubles(40, 24, 0, 4) == 2 * 768 * 2
+    assert pt.variance_workspace_doubles(40, 24, 3, 4) == 768 * 2
+    assert pt.variance_workspace_doubles(0, 24) == 0 and pt.variance_workspace_doubles(40, 0) == 0
+    assert pt.variance_workspace_doubles(40, 24, 3, 3) == 0 and pt.variance_workspace_doubles(40, 24, 0, 0) == 0
+    assert "0.4.3" in pt.version() and pt.lib().pt_abi_version() == 4
+
+
+BAD_DENOISE = {
+    "null_rgb": dict(rgb=None),
+    "null_normal": dict(normal=None),
+    "null_depth": dict(depth=None),
+    "null_variance": dict(variance=None),
+    "null_albedo_with_demodulation": dict(albedo=None),
+    "null_out": dict(out=None),
+    "zero_width": dict(w=0),
+    "zero_height": dict(h=0),
+    "no_iterations": dict(iterations=0),
+    "nine_iterations": dict(iterations=9),
+    "unknown_flag": dict(flags=2),
+    "sigma_normal_zero": dict(sn=0.0),
+    "sigma_depth_nan": dict(sd=NAN),
+    "sigma_variance_zero": dict(sv=0.0),
+    "sigma_variance_negative": dict(sv=-8.0),
+    "sigma_variance_nan": dict(sv=NAN),
+}
+
+
+@pytest.mark.parametrize("case", list(BAD_DENOISE))
+def test_denoise_variance_argument_errors(pt, case):
+    w, h = 8, 4
+    a = dict(rgb=np.ones((w * h, 3)), albedo=np.ones((w * h, 3)), normal=np.zeros((w * h, 3)),
+             depth=np.ones((w * h, 3)), variance=np.ones((w * h, 3)), out=np.full((w * h, 3), -7.25), w=w, h=h,
+             iterations=5, sn=0.5, sd=0.1, sv=8.0, flags=1)
+    out = a["out"]
+    a.update(BAD_DENOISE[case])
+    ptr = {k: None if a[k] is None else a[k].ctypes.data_as(d)
+           for k in ("rgb", "albedo", "normal", "depth", "variance", "out")}
+    rc = pt.lib().pt_denoise_variance(-1, ptr["rgb"], ptr["albedo"], ptr["normal"], ptr["depth"], ptr["variance"],
+                                      a["w"], a["h"], a["iterations"], a["sn"], a["sd"], a["sv"], a["flags"], ptr["out"])
+    assert rc == pt.PT_ERR_INVALID, (case, rc)
+    assert pt.lib().pt_last_error()
+    assert np.all(out == -7.25)  # a refused call writes nothing
+
+
+def test_device_forms_argument_errors(pt):
+    """The device forms' checks come before their first HIP call: the pointers are never dereferenced on the host."""
+    w, h = 8, 4
+    count = w * h * 3
+    buf = np.zeros(count + w * h * 12 + 2)
+    base = buf.ctypes.data
+    work = (base + count * 8 + 15) & ~15
+    L = pt.lib()
+
+    def dn(work_ptr=work, var=base, iterations=5, sv=8.0, out=base):
+        return L.pt_denoise_variance_device(-1, base, base, base, base, var, w, h, iterations, 0.5, 0.1, sv, 1, out,
+                                            work_ptr, None)
+
+    assert dn(work_ptr=None) == pt.PT_ERR_INVALID
+    assert dn(work_ptr=work + 8) == pt.PT_ERR_INVALID and b"aligned" in L.pt_last_error()
+    assert dn(var=None) == pt.PT_ERR_INVALID and dn(out=None) == pt.PT_ERR_INVALID
+    assert dn(iterations=9) == pt.PT_ERR_INVALID
+    for sv in (0.0, -1.0, NAN):
+        assert dn(sv=sv) == pt.PT_ERR_INVALID and b"sigma_variance" in L.pt_last_error()
+
+    def win(out=base, cnt=count, n_k=2, n=16, window=1, windows=8, wk=work, var=base):
+        return L.pt_variance_window_device(-1, out, cnt, n_k, n, window, windows, wk, var, None)
+
+    for bad in (dict(out=None), dict(wk=None), dict(var=None), dict(cnt=0), dict(n_k=0), dict(n_k=17), dict(window=0),
+                dict(window=9), dict(windows=1), dict(windows=0), dict(windows=17, window=17)):
+        assert win(**bad) == pt.PT_ERR_INVALID, bad
+        assert L.pt_last_error()
+    assert np.all(buf == 0.0)
+
+
+def test_render_variance_argument_errors(pt, cornell_text):
+    """The renderer forms refuse a null renderer, camera or buffer, a zero size, a bad window count and a bad rank
+    before anything else (no renderer can be made without a GPU, so the others are tried on the GPU)."""
+    L = pt.lib()
+    sc = pt.Scene.from_json(cornell_text)
+    cam = C.byref(sc.camera()._c)
+    w, h = 8, 4
+    rgb, var = np.full((w * h, 3), -7.25), np.full((w * h, 3), -7.25)
+    rc = L.pt_render_variance(None, cam, w, h, 16, 1, 8, rgb.ctypes.data_as(d), var.ctypes.data_as(d))
+    assert rc == pt.PT_ERR_INVALID
+    assert L.pt_render_variance_device(None, cam, w, h, 16, 1, 0, 1, 8, rgb.ctypes.data, var.ctypes.data,
+                                       rgb.ctypes.data, None) == pt.PT_ERR_INVALID
+    assert np.all(rgb == -7.25) and np.all(var == -7.25)

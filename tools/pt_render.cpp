@@ -4,7 +4,7 @@
 // (src/bin/main.rs:71-83, 281-289).  This does the same in one go, on the GPU:
 //
 //   pt_render scene.json [spp [w h]] [-d depth] [-s seed] [-o image.png|image.ppm] [-f frame.f64]
-//             [-c checkpoint -n window_spp [-x windows]] [-a prefix] [-D denoised.png]
+//             [-c checkpoint -n window_spp [-x windows]] [-a prefix] [-D denoised.png] [-V var.f64 [-W windows]]
 //
 // -o: the encoded image (PNG, or PPM by extension; default rendered.png, the name of the reference's "F" save).
 // -f: the linear f64 frame (w*h*3, row-major), for comparisons.
@@ -20,6 +20,11 @@
 //     sigma_normal 0.5, sigma_depth 0.1, no colour term, demodulated), as a PNG through the display encode; with -f
 //     also the linear f64 frame as denoised.png.f64.  The planes are -a's when it was given, else they are rendered
 //     on the device for this.  -o and -f still get the noisy frame.  (-d is the depth, so the letter is a capital.)
+// -V: the variance of each pixel's mean, per channel, estimated from the frame's own sample windows
+//     (pt_render_variance), as linear f64 in -f's format (w*h*3, row-major); the frame is the same bits.
+//     -W: the number of windows (default 8, or spp when that is less).  With -V, -D uses the denoiser's variance
+//     term (pt_denoise_variance_device, sigma_variance 8).  -V with -c is a usage error: the accumulation state is
+//     not checkpointed.
 // Exit status: 0 done, 1 error (the library's message on stderr), 2 usage, 3 stopped with a checkpoint.
 #include <hip/hip_runtime_api.h>
 
@@ -40,7 +45,8 @@ namespace {
 int usage() {
     std::fprintf(stderr,
                  "usage: pt_render scene.json [spp [w h]] [-d depth] [-s seed] [-o image.png|.ppm] [-f frame.f64]\n"
-                 "                 [-c checkpoint -n window_spp [-x windows]] [-a aov_prefix] [-D denoised.png]\n");
+                 "                 [-c checkpoint -n window_spp [-x windows]] [-a aov_prefix] [-D denoised.png]\n"
+                 "                 [-V variance.f64 [-W windows]]   (-V cannot be combined with -c)\n");
     return 2;
 }
 
@@ -84,9 +90,9 @@ bool ends_with(const std::string &s, const char *suf) {
 
 int main(int argc, char **argv) {
     std::vector<const char *> pos;
-    uint32_t depth = 50, window = 0, stop_after = 0;
+    uint32_t depth = 50, window = 0, stop_after = 0, var_windows = 0;
     uint64_t seed = 1;
-    std::string out_img = "rendered.png", out_f64, ckpt, aov, denoised;
+    std::string out_img = "rendered.png", out_f64, ckpt, aov, denoised, out_var;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto val = [&](const char *name) -> const char * {
@@ -104,11 +110,14 @@ int main(int argc, char **argv) {
         else if (a == "-n") window = (uint32_t)std::strtoul(val("-n"), nullptr, 10);
         else if (a == "-a") aov = val("-a");
         else if (a == "-D") denoised = val("-D");
+        else if (a == "-V") out_var = val("-V");
+        else if (a == "-W") var_windows = (uint32_t)std::strtoul(val("-W"), nullptr, 10);
         else if (a == "-x") stop_after = (uint32_t)std::strtoul(val("-x"), nullptr, 10);
         else if (a.size() > 1 && a[0] == '-') return usage();
         else pos.push_back(argv[i]);
     }
     if (pos.empty() || pos.size() == 3 || pos.size() > 4 || (!ckpt.empty() && window == 0)) return usage();
+    if (!out_var.empty() && !ckpt.empty()) return usage();
     const uint32_t spp = pos.size() >= 2 ? (uint32_t)std::strtoul(pos[1], nullptr, 10) : 100;  // the GUI's 100
     const uint32_t w = pos.size() == 4 ? (uint32_t)std::strtoul(pos[2], nullptr, 10) : 1600;    // main.rs:26
     const uint32_t h = pos.size() == 4 ? (uint32_t)std::strtoul(pos[3], nullptr, 10) : 900;
@@ -126,8 +135,15 @@ int main(int argc, char **argv) {
     if ((rc = pt_scene_camera(scene, &cam))) return fail("camera", rc);
     if ((rc = pt_renderer_create(scene, -1, depth, &r))) return fail("renderer", rc);
     const size_t npix = (size_t)w * h;
-    std::vector<double> rgb(npix * 3);
-    if (ckpt.empty()) {
+    std::vector<double> rgb(npix * 3), variance;
+    if (!out_var.empty()) {
+        // the frame in sample windows, with the variance of each pixel's mean beside it
+        variance.resize(npix * 3);
+        if (var_windows == 0) var_windows = spp < 8 ? spp : 8;
+        if ((rc = pt_render_variance(r, &cam, w, h, spp, seed, var_windows, rgb.data(), variance.data())))
+            return fail("render with variance", rc);
+        if (!write_doubles(out_var, variance)) return 1;
+    } else if (ckpt.empty()) {
         if ((rc = pt_render_start(r, &cam, w, h, spp, seed)) || (rc = pt_render_step(r, rgb.data(), 1)) != 1)
             return fail("render", rc);
     } else {
@@ -229,10 +245,11 @@ int main(int argc, char **argv) {
     }
     if (!denoised.empty()) {
         // on the device: the frame, the three planes and the workspace in one allocation
+        // (and the variance plane after the workspace, with -V)
         const size_t plane = npix * 3, work = pt_denoise_workspace_doubles(w, h);
         double *d = nullptr;
         uint8_t *d_rgba = nullptr;
-        if (hipMalloc((void **)&d, (plane * 4 + work) * sizeof(double)) != hipSuccess ||
+        if (hipMalloc((void **)&d, (plane * (variance.empty() ? 4 : 5) + work) * sizeof(double)) != hipSuccess ||
             hipMalloc((void **)&d_rgba, npix * 4) != hipSuccess ||
             hipMemcpy(d, rgb.data(), plane * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
             std::fprintf(stderr, "pt_render: no device memory for the denoiser\n");
@@ -244,9 +261,17 @@ int main(int argc, char **argv) {
         } else if ((rc = pt_render_aov_device(r, &cam, w, h, spp, seed, 0, 1, alb, nrm, dep, nullptr))) {
             return fail("guide planes", rc);
         }
-        if ((rc = pt_denoise_device(-1, d, alb, nrm, dep, w, h, 5, 0.5, 0.1, 0.0, PT_DENOISE_DEMODULATE, d, dep + plane,
-                                    nullptr)))
-            return fail("denoise", rc);
+        if (variance.empty()) {
+            if ((rc = pt_denoise_device(-1, d, alb, nrm, dep, w, h, 5, 0.5, 0.1, 0.0, PT_DENOISE_DEMODULATE, d,
+                                        dep + plane, nullptr)))
+                return fail("denoise", rc);
+        } else {
+            double *d_var = dep + plane + work;
+            if (hipMemcpy(d_var, variance.data(), plane * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return 1;
+            if ((rc = pt_denoise_variance_device(-1, d, alb, nrm, dep, d_var, w, h, 5, 0.5, 0.1, 8.0,
+                                                 PT_DENOISE_DEMODULATE, d, dep + plane, nullptr)))
+                return fail("denoise", rc);
+        }
         if ((rc = pt_encode_rgba8_device(-1, d, npix, d_rgba, nullptr))) return fail("encode", rc);
         std::vector<uint8_t> rgba(npix * 4);
         std::vector<double> clean(plane);
