@@ -369,6 +369,60 @@ int pt_denoise_variance(int device, const double *rgb, const double *albedo, con
                         uint32_t iterations, double sigma_normal, double sigma_depth, double sigma_variance,
                         uint32_t flags, double *out);
 
+/* ---- adaptive sampling: every 16x16 tile stops at a noise target ---------- */
+/* The frame is rendered in sample windows of `window` samples, up to
+ * max_samples (the last window may be short; max_samples > window, so there
+ * are two windows at least).  After each window every tile that is still
+ * active is judged from the windows' running sums: the batch-means variance of
+ * each pixel's mean (the estimate of pt_render_variance), summed over the tile
+ * as the variance of its luminance, against the tile's mean luminance floored
+ * at luminance_floor.  A tile stops when that relative standard error is at
+ * most `threshold`, at the second window and e_k >= min_samples at the
+ * earliest, or when it reaches max_samples; its pixels then are, bit for bit,
+ * those of pt_render_device's frame at the tile's own sample count, and the
+ * tile is neither rendered nor written again.  threshold 0 runs every tile
+ * that is not constant to max_samples; +inf stops every tile at the first
+ * evaluation.  The arithmetic, step by step, is in
+ * rs-pathtracing_amd/csrc/pt_adaptive.hpp and DESIGN.md 3.10: f64, one fixed
+ * order, bit for bit the numpy restatement in tests/adaptiveref.py.
+ * d_out and d_variance (may be NULL; the variance of each element's mean at
+ * the tile's sample count) have pt_render_device's layout, the shard layout
+ * included (a padding element is 0); d_tile_samples (and d_tile_error, may be
+ * NULL: the squared relative standard error the tile stopped with) have
+ * pt_shard_tiles(width, height, rank, world) entries in the rank's tile order;
+ * d_work holds pt_adaptive_workspace_doubles doubles (3 * count, count as for
+ * pt_variance_workspace_doubles; need not be cleared), 16-byte aligned.
+ * Between windows the still-active tiles are grouped into runs, one render
+ * launch each; runs with at most merge_gap stopped tiles between them are
+ * joined (their stopped tiles are rendered again and ignored: the frame does
+ * not depend on merge_gap, only the time does).  samples_rendered (may be
+ * NULL) receives the pixel-samples launched, that waste included.  The call
+ * blocks: it synchronises hip_stream once per window, because the host picks
+ * the next launches.  Recommended: window 8, min_samples 0, luminance_floor
+ * 0.01, merge_gap 1024.  PT_ERR_INVALID, the call writing nothing: a NULL
+ * required pointer, a zero size or window, max_samples <= window or above
+ * 2^32 - 2, min_samples > max_samples, threshold or luminance_floor negative
+ * or NaN, rank >= world (or a rank that holds no tile), a misaligned
+ * workspace.  PT_ERR_STATE while a pt_render_start frame is in flight.  The
+ * accumulation state is not checkpointed.  Stopping on a variance estimated
+ * from the same samples biases the frame slightly dark where bright paths
+ * are rare.  (Library 0.4.3; no ABI change.) */
+#define PT_ADAPTIVE_WINDOW 8            /* the recommended defaults (Python's and pt_render's) */
+#define PT_ADAPTIVE_LUMINANCE_FLOOR 0.01
+#define PT_ADAPTIVE_MERGE_GAP 1024
+/* 3 * count; 0 on a zero size or rank >= world */
+size_t pt_adaptive_workspace_doubles(uint32_t width, uint32_t height, uint32_t rank, uint32_t world);
+int pt_render_adaptive_device(pt_renderer *r, const pt_camera *camera, uint32_t width, uint32_t height,
+                              uint32_t window, uint32_t min_samples, uint32_t max_samples, double threshold,
+                              double luminance_floor, uint32_t merge_gap, uint64_t seed, uint32_t rank,
+                              uint32_t world, double *d_out, double *d_variance, uint32_t *d_tile_samples,
+                              double *d_tile_error, double *d_work, void *hip_stream, uint64_t *samples_rendered);
+/* the same into host buffers (world 1); allocates, copies, blocks */
+int pt_render_adaptive(pt_renderer *r, const pt_camera *camera, uint32_t width, uint32_t height, uint32_t window,
+                       uint32_t min_samples, uint32_t max_samples, double threshold, double luminance_floor,
+                       uint32_t merge_gap, uint64_t seed, double *rgb, double *variance, uint32_t *tile_samples,
+                       double *tile_error, uint64_t *samples_rendered);
+
 /* ---- resumable frames (checkpoint / resume) ----------------------------- */
 /* The reference renders a frame in one go and keeps nothing between runs
  * (Renderer::render, src/renderer/mod.rs:67-114; its GUI saves only the

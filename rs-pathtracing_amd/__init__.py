@@ -54,7 +54,11 @@ EXPORTS = [
     "pt_denoise_workspace_doubles", "pt_denoise_device", "pt_denoise",
     "pt_variance_workspace_doubles", "pt_variance_window_device", "pt_render_variance_device", "pt_render_variance",
     "pt_denoise_variance_device", "pt_denoise_variance",
+    "pt_adaptive_workspace_doubles", "pt_render_adaptive_device", "pt_render_adaptive",
 ]
+ADAPTIVE_WINDOW = 8  # the recommended defaults of pt_render_adaptive (rs_pathtracing.h)
+ADAPTIVE_FLOOR = 0.01
+ADAPTIVE_MERGE_GAP = 1024
 DENOISE_DEMODULATE = 1  # PT_DENOISE_DEMODULATE
 DENOISE_MAX_ITERATIONS = 8  # PT_DENOISE_MAX_ITERATIONS
 ABI_VERSION = 4  # PT_ABI_VERSION this binding is written for
@@ -175,6 +179,12 @@ def lib():
                                                  C.c_double, u32, vp, vp, vp]),
         "pt_denoise_variance": (C.c_int, [C.c_int, d, d, d, d, d, u32, u32, u32, C.c_double, C.c_double, C.c_double,
                                           u32, d]),
+        "pt_adaptive_workspace_doubles": (sz, [u32, u32, u32, u32]),
+        "pt_render_adaptive_device": (C.c_int, [vp, C.POINTER(CameraStruct), u32, u32, u32, u32, u32, C.c_double,
+                                                C.c_double, u32, u64, u32, u32, vp, vp, vp, vp, vp, vp,
+                                                C.POINTER(u64)]),
+        "pt_render_adaptive": (C.c_int, [vp, C.POINTER(CameraStruct), u32, u32, u32, u32, u32, C.c_double, C.c_double,
+                                         u32, u64, d, d, C.POINTER(u32), d, C.POINTER(u64)]),
         "pt_checkpoint_save": (C.c_int, [C.c_char_p, C.POINTER(CheckpointStruct), d]),
         "pt_checkpoint_load": (C.c_int, [C.c_char_p, C.POINTER(CheckpointStruct), d, u64]),
         "pt_shard_tiles": (u32, [u32, u32, u32, u32]),
@@ -497,6 +507,48 @@ class HipRenderer(Renderer):
                                                C.c_void_p(variance_ptr or None), C.c_void_p(work_ptr or None),
                                                C.c_void_p(stream_ptr)))
 
+    # ---- adaptive sampling: every tile stops at a noise target (pt_render_adaptive) ----
+    def render_adaptive(self, camera: Camera, img_params: ImageParams, max_samples: int, threshold: float,
+                        window: int = ADAPTIVE_WINDOW, min_samples: int = 0, luminance_floor: float = ADAPTIVE_FLOOR,
+                        merge_gap: int = ADAPTIVE_MERGE_GAP, seed=None, return_samples_rendered: bool = False):
+        """(rgb, tile_samples, tile_error, variance): the frame rendered in windows of `window` samples, every
+        16x16 tile stopped once the relative standard error of its luminance is at most `threshold` (or at
+        max_samples).  rgb and variance are (w*h, 3) float64; tile_samples (uint32) and tile_error (float64, the
+        squared relative standard error at the stop) have one entry per tile, row-major.  A tile's pixels are
+        render(camera, img_params, tile_samples[tile], seed)'s, bit for bit.  See pt_render_adaptive."""
+        s = self.seed if seed is None else int(seed)
+        w, h = img_params.width, img_params.height
+        n, nt = w * h, ((w + 15) // 16) * ((h + 15) // 16)
+        rgb, var = np.zeros((n, 3), dtype=np.float64), np.zeros((n, 3), dtype=np.float64)
+        ts, te = np.zeros(nt, dtype=np.uint32), np.zeros(nt, dtype=np.float64)
+        launched = C.c_uint64(0)
+        _check(lib().pt_render_adaptive(self._h, C.byref(camera._c), w, h, int(window), int(min_samples),
+                                        int(max_samples), float(threshold), float(luminance_floor), int(merge_gap),
+                                        s, _dptr(rgb), _dptr(var), ts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                        _dptr(te), C.byref(launched)))
+        if return_samples_rendered:
+            return rgb, ts, te, var, int(launched.value)
+        return rgb, ts, te, var
+
+    def render_adaptive_device(self, camera: Camera, width: int, height: int, max_samples: int, threshold: float,
+                               seed: int, rank: int, world: int, out_ptr: int, variance_ptr: int,
+                               tile_samples_ptr: int, tile_error_ptr: int, work_ptr: int, stream_ptr: int = 0,
+                               window: int = ADAPTIVE_WINDOW, min_samples: int = 0,
+                               luminance_floor: float = ADAPTIVE_FLOOR, merge_gap: int = ADAPTIVE_MERGE_GAP) -> int:
+        """render_adaptive into device buffers of the caller's, render_device's layout (variance_ptr and
+        tile_error_ptr may be 0), with adaptive_workspace_doubles(width, height, rank, world) doubles at work_ptr;
+        blocks, synchronising stream_ptr once per window.  Returns the pixel-samples launched
+        (pt_render_adaptive_device)."""
+        launched = C.c_uint64(0)
+        _check(lib().pt_render_adaptive_device(self._h, C.byref(camera._c), width, height, int(window),
+                                               int(min_samples), int(max_samples), float(threshold),
+                                               float(luminance_floor), int(merge_gap), seed, rank, world,
+                                               C.c_void_p(out_ptr or None), C.c_void_p(variance_ptr or None),
+                                               C.c_void_p(tile_samples_ptr or None),
+                                               C.c_void_p(tile_error_ptr or None), C.c_void_p(work_ptr or None),
+                                               C.c_void_p(stream_ptr), C.byref(launched)))
+        return int(launched.value)
+
     # ---- probes --------------------------------------------------------
     def closest_hit(self, rays: np.ndarray, min_t: float = 0.001, max_t: float = float("inf")) -> np.ndarray:
         rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
@@ -718,6 +770,12 @@ def variance_workspace_doubles(width: int, height: int, rank: int = 0, world: in
     """Doubles of device workspace the variance accumulation needs for one rank's d_out: 2 per element
     (pt_variance_workspace_doubles)."""
     return int(lib().pt_variance_workspace_doubles(int(width), int(height), int(rank), int(world)))
+
+
+def adaptive_workspace_doubles(width: int, height: int, rank: int = 0, world: int = 1) -> int:
+    """Doubles of device workspace an adaptive frame needs for one rank's d_out: 3 per element
+    (pt_adaptive_workspace_doubles)."""
+    return int(lib().pt_adaptive_workspace_doubles(int(width), int(height), int(rank), int(world)))
 
 
 def variance_window_device(out_ptr: int, count: int, n_k: int, samples_number: int, window: int, windows: int,

@@ -20,6 +20,7 @@
 
 #include "../../include/rs_pathtracing.h"
 #include "pt_accel.hpp"
+#include "pt_adaptive.hpp"
 #include "pt_aov.hpp"
 #include "pt_denoise.hpp"
 #include "pt_kernel.hpp"
@@ -1195,6 +1196,119 @@ int pt_denoise_variance(int device, const double *rgb, const double *albedo, con
         return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     HIP_TRY(hipMemcpy(out, dev[0].p, count * sizeof(double), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// ---- adaptive sampling: every tile stops at a noise target (pt_adaptive.hpp) ----
+namespace {
+static_assert(PT_ADAPTIVE_WINDOW == ADAPTIVE_WINDOW && PT_ADAPTIVE_LUMINANCE_FLOOR == ADAPTIVE_FLOOR &&
+                  PT_ADAPTIVE_MERGE_GAP == ADAPTIVE_MERGE_GAP,
+              "the header states the recommended defaults");
+int adaptive_refused(const void *r, const void *cam, uint32_t w, uint32_t h, uint32_t window, uint32_t min_samples,
+                     uint32_t max_samples, double threshold, double luminance_floor, uint32_t rank, uint32_t world,
+                     const void *out, const void *tile_samples) {
+    if (!r || !cam || !out || !tile_samples) return fail(PT_ERR_INVALID, "null argument");
+    if (w == 0 || h == 0 || window == 0) return fail(PT_ERR_INVALID, "width, height and window must be > 0");
+    if (max_samples <= window) return fail(PT_ERR_INVALID, "max_samples must be above window (two windows at least)");
+    if (max_samples > 0xfffffffeu) return fail(PT_ERR_INVALID, "max_samples must be at most 2^32 - 2");
+    if (min_samples > max_samples) return fail(PT_ERR_INVALID, "min_samples must be at most max_samples");
+    if (!(threshold >= 0.0)) return fail(PT_ERR_INVALID, "threshold must be >= 0");
+    if (!(luminance_floor >= 0.0)) return fail(PT_ERR_INVALID, "luminance_floor must be >= 0");
+    if (world == 0 || rank >= world) return fail(PT_ERR_INVALID, "rank must be < world");
+    if (pt_shard_tiles(w, h, rank, world) == 0 || adaptive_workspace_doubles(variance_count(w, h, rank, world)) == 0)
+        return fail(PT_ERR_INVALID, "the frame is too large for the adaptive pass (or the rank has no tile)");
+    return PT_OK;
+}
+}  // namespace
+
+size_t pt_adaptive_workspace_doubles(uint32_t w, uint32_t h, uint32_t rank, uint32_t world) {
+    return adaptive_workspace_doubles(variance_count(w, h, rank, world));
+}
+
+int pt_render_adaptive_device(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t window,
+                              uint32_t min_samples, uint32_t max_samples, double threshold, double luminance_floor,
+                              uint32_t merge_gap, uint64_t seed, uint32_t rank, uint32_t world, double *d_out,
+                              double *d_variance, uint32_t *d_tile_samples, double *d_tile_error, double *d_work,
+                              void *stream, uint64_t *samples_rendered) {
+    if (int rc = adaptive_refused(r, cam, w, h, window, min_samples, max_samples, threshold, luminance_floor, rank,
+                                  world, d_out, d_tile_samples))
+        return rc;
+    if (!d_work) return fail(PT_ERR_INVALID, "null argument");
+    if (((uintptr_t)d_work & 15u) != 0) return fail(PT_ERR_INVALID, "the workspace must be 16-byte aligned");
+    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
+    GpuShare &g = r->gpus[0];
+    HIP_TRY(hipSetDevice(g.device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t count = (size_t)variance_count(w, h, rank, world);
+    const uint32_t ntiles = pt_shard_tiles(w, h, rank, world);
+    // Every window is a window of a frame one sample longer than the cap, so s_end < spp always holds and the render
+    // leaves sums, never means: spp reaches only wf_reduce's final division and the engine choice (a windowed frame
+    // always runs the wavefront engine; the samples' keys come from their indices).
+    FrameParams P = frame_params(r, *cam, w, h, max_samples + 1, seed);
+    P.rank = rank;
+    P.world = world;
+    P.compact = world > 1 ? 1 : 0;
+    const dev::AdaptiveGeom geom{w, h, rank, world, P.tiles_x, P.compact};
+    std::vector<uint8_t> active(ntiles, 1);
+    std::vector<uint32_t> pixels(ntiles), stopped(ntiles);
+    for (uint32_t i = 0; i < ntiles; i++) pixels[i] = dev::adaptive_tile_pixels(geom, i);
+    uint64_t launched = 0;
+    const uint32_t windows = adaptive_windows(window, max_samples);
+    for (uint32_t k = 1; k <= windows; k++) {
+        const dev::AdaptiveConsts c = adaptive_consts(k, window, min_samples, max_samples, threshold, luminance_floor);
+        P.s_begin = adaptive_edge(k - 1, window, max_samples);
+        P.s_end = c.e_k;
+        // the window's samples of the still-active tiles, into the sums plane: one launch per run
+        const std::vector<AdaptiveRun> runs = adaptive_runs(active.data(), ntiles, merge_gap);
+        if (runs.empty()) break;
+        for (const AdaptiveRun &run : runs) {
+            P.tile_begin = run.begin;
+            P.tile_count = run.count;
+            if (int rc = render_on(g, P, d_work, st)) return rc;
+            for (uint32_t i = run.begin; i < run.begin + run.count; i++)
+                launched += (uint64_t)pixels[i] * (P.s_end - P.s_begin);
+        }
+        HIP_TRY(launch_adaptive_tiles(geom, ntiles, count, c, k == 1, d_work, d_out, d_variance, d_tile_samples,
+                                      d_tile_error, st));
+        if (!c.evaluate || c.cap) continue;  // no tile can have stopped, or every tile has
+        // the host decides the next window's launches: 4 bytes per tile
+        HIP_TRY(hipMemcpyAsync(stopped.data(), d_tile_samples, (size_t)ntiles * sizeof(uint32_t),
+                               hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (uint32_t i = 0; i < ntiles; i++) active[i] = stopped[i] == 0;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (samples_rendered) *samples_rendered = launched;
+    return PT_OK;
+}
+
+int pt_render_adaptive(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t window,
+                       uint32_t min_samples, uint32_t max_samples, double threshold, double luminance_floor,
+                       uint32_t merge_gap, uint64_t seed, double *rgb, double *variance, uint32_t *tile_samples,
+                       double *tile_error, uint64_t *samples_rendered) {
+    if (int rc = adaptive_refused(r, cam, w, h, window, min_samples, max_samples, threshold, luminance_floor, 0, 1,
+                                  rgb, tile_samples))
+        return rc;
+    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
+    HIP_TRY(hipSetDevice(r->device()));
+    const size_t count = (size_t)w * h * 3, ntiles = pt_shard_tiles(w, h, 0, 1);
+    DevBuf<double> out, var, err, work;  // staging, freed on return
+    DevBuf<uint32_t> ts;
+    HIP_TRY(out.alloc(count));
+    if (variance) HIP_TRY(var.alloc(count));
+    if (tile_error) HIP_TRY(err.alloc(ntiles));
+    HIP_TRY(ts.alloc(ntiles));
+    HIP_TRY(work.alloc(adaptive_workspace_doubles(count)));
+    uint64_t launched = 0;
+    if (int rc = pt_render_adaptive_device(r, cam, w, h, window, min_samples, max_samples, threshold, luminance_floor,
+                                           merge_gap, seed, 0, 1, out.p, var.p, ts.p, err.p, work.p, r->stream(),
+                                           &launched))
+        return rc;
+    HIP_TRY(hipMemcpy(rgb, out.p, count * sizeof(double), hipMemcpyDeviceToHost));
+    if (variance) HIP_TRY(hipMemcpy(variance, var.p, count * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tile_samples, ts.p, ntiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (tile_error) HIP_TRY(hipMemcpy(tile_error, err.p, ntiles * sizeof(double), hipMemcpyDeviceToHost));
+    if (samples_rendered) *samples_rendered = launched;
     return PT_OK;
 }
 

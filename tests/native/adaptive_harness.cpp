@@ -1,0 +1,89 @@
+// Test-only host build of adaptive sampling's per-tile pass (pt_adaptive.hpp): the functions the adaptive_tiles
+// kernel runs per lane and per tile (dev::adaptive_pixel_at, adaptive_element, adaptive_variance, adaptive_pixel,
+// adaptive_converged), compiled for the CPU and run over every tile of a rank's list with the host's own constants;
+// the tile sums are the kernel's tree, written as its definition: for d = 1, 2, ..., 128, a[i] += a[i + d] for every
+// i that is a multiple of 2d.  Also adaptive_runs and the window edges.  tests/test_adaptive_host.py compares the
+// results with tests/adaptiveref.py bit for bit.  Never used by the product.
+#include <vector>
+
+#include "../../rs-pathtracing_amd/csrc/pt_adaptive.hpp"
+
+using namespace pt;
+
+static double tree256(double *a) {
+    for (uint32_t d = 1; d <= 128; d *= 2)
+        for (uint32_t i = 0; i < 256; i += 2 * d) a[i] = a[i] + a[i + d];
+    return a[0];
+}
+
+template <bool FIRST>
+static void window_on_host(const dev::AdaptiveGeom &g, uint32_t ntiles, size_t count, const dev::AdaptiveConsts &k,
+                           double *work, double *out, double *variance, uint32_t *tile_samples, double *tile_error) {
+    const double *sums = work;
+    double *prev = work + count, *q = prev + count;
+    const bool evaluate = !FIRST && k.evaluate != 0;
+    for (uint32_t ti = 0; ti < ntiles; ti++) {
+        if (!FIRST && tile_samples[ti] != 0) continue;
+        double S[256][3], var[256][3], vl[256], l[256];
+        size_t at[256];
+        bool inside[256];
+        for (uint32_t i = 0; i < 256; i++) {
+            inside[i] = dev::adaptive_pixel_at(g, ti, i, &at[i]);
+            vl[i] = l[i] = 0.0;
+            for (int c = 0; c < 3; c++) S[i][c] = var[i][c] = 0.0;
+            if (!inside[i]) continue;
+            for (int c = 0; c < 3; c++) {
+                S[i][c] = sums[at[i] + c];
+                const double qn = dev::adaptive_element<FIRST>(S[i][c], k, &prev[at[i] + c], &q[at[i] + c]);
+                if (evaluate) var[i][c] = dev::adaptive_variance(S[i][c], qn, k);
+            }
+            if (evaluate) dev::adaptive_pixel(S[i], var[i], k, &vl[i], &l[i]);
+        }
+        if (FIRST) {
+            tile_samples[ti] = 0;
+            continue;
+        }
+        if (!evaluate) continue;
+        const double V = tree256(vl), Lm = tree256(l);
+        double err2;
+        const bool converged = dev::adaptive_converged(V, Lm, (double)dev::adaptive_tile_pixels(g, ti), k, &err2);
+        if (!converged && !k.cap) continue;
+        for (uint32_t i = 0; i < 256; i++) {
+            if (!inside[i] && !g.compact) continue;
+            for (int c = 0; c < 3; c++) {
+                out[at[i] + c] = inside[i] ? S[i][c] / k.ek : 0.0;
+                if (variance) variance[at[i] + c] = inside[i] ? var[i][c] : 0.0;
+            }
+        }
+        tile_samples[ti] = k.e_k;
+        if (tile_error) tile_error[ti] = err2;
+    }
+}
+
+// Window k's pass over the ntiles tiles of rank's list (world > 1: the compact layout), on a workspace whose sums
+// plane the caller has filled; launch_adaptive_tiles' arguments.  Returns the doubles of workspace it used.
+extern "C" size_t ad_window(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint32_t ntiles, size_t count,
+                            uint32_t k, uint32_t window, uint32_t min_samples, uint32_t max_samples, double threshold,
+                            double luminance_floor, double *work, double *out, double *variance,
+                            uint32_t *tile_samples, double *tile_error) {
+    const dev::AdaptiveGeom g{w, h, rank, world, (w + TILE - 1) / TILE, world > 1 ? 1u : 0u};
+    const dev::AdaptiveConsts c = adaptive_consts(k, window, min_samples, max_samples, threshold, luminance_floor);
+    if (k == 1) window_on_host<true>(g, ntiles, count, c, work, out, variance, tile_samples, tile_error);
+    else window_on_host<false>(g, ntiles, count, c, work, out, variance, tile_samples, tile_error);
+    return adaptive_workspace_doubles(count);
+}
+
+extern "C" uint32_t ad_edge(uint32_t k, uint32_t window, uint32_t max_samples) {
+    return adaptive_edge(k, window, max_samples);
+}
+extern "C" uint32_t ad_windows(uint32_t window, uint32_t max_samples) { return adaptive_windows(window, max_samples); }
+
+// adaptive_runs into runs[2 * i] = begin, runs[2 * i + 1] = count (room for ntiles runs); returns the number of runs.
+extern "C" uint32_t ad_runs(const uint8_t *active, uint32_t ntiles, uint32_t merge_gap, uint32_t *runs) {
+    const std::vector<AdaptiveRun> r = adaptive_runs(active, ntiles, merge_gap);
+    for (size_t i = 0; i < r.size(); i++) {
+        runs[2 * i] = r[i].begin;
+        runs[2 * i + 1] = r[i].count;
+    }
+    return (uint32_t)r.size();
+}

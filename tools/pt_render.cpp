@@ -5,6 +5,7 @@
 //
 //   pt_render scene.json [spp [w h]] [-d depth] [-s seed] [-o image.png|image.ppm] [-f frame.f64]
 //             [-c checkpoint -n window_spp [-x windows]] [-a prefix] [-D denoised.png] [-V var.f64 [-W windows]]
+//             [-A threshold [-B window] [-M tiles.u32]]
 //
 // -o: the encoded image (PNG, or PPM by extension; default rendered.png, the name of the reference's "F" save).
 // -f: the linear f64 frame (w*h*3, row-major), for comparisons.
@@ -25,6 +26,13 @@
 //     -W: the number of windows (default 8, or spp when that is less).  With -V, -D uses the denoiser's variance
 //     term (pt_denoise_variance_device, sigma_variance 8).  -V with -c is a usage error: the accumulation state is
 //     not checkpointed.
+// -A: adaptive sampling (pt_render_adaptive): spp is the cap, and every 16x16 tile stops once the
+//     relative standard error of its luminance is at most the threshold (0: run every tile that is not constant to
+//     the cap; inf: stop every tile at the second window), judged after each window of -B samples (default 8;
+//     min_samples 0, luminance floor 0.01, the library's recommended merge_gap).  -M: the samples each tile stopped
+//     at, as uint32, tiles row-major.  With -A, -V writes the adaptive frame's variance plane (each pixel's at its
+//     tile's own sample count) and -D uses it.  -A with -c or -W, and -B or -M without -A, are usage errors: the
+//     accumulation state is not checkpointed.
 // Exit status: 0 done, 1 error (the library's message on stderr), 2 usage, 3 stopped with a checkpoint.
 #include <hip/hip_runtime_api.h>
 
@@ -46,7 +54,8 @@ int usage() {
     std::fprintf(stderr,
                  "usage: pt_render scene.json [spp [w h]] [-d depth] [-s seed] [-o image.png|.ppm] [-f frame.f64]\n"
                  "                 [-c checkpoint -n window_spp [-x windows]] [-a aov_prefix] [-D denoised.png]\n"
-                 "                 [-V variance.f64 [-W windows]]   (-V cannot be combined with -c)\n");
+                 "                 [-V variance.f64 [-W windows]]   (-V cannot be combined with -c)\n"
+                 "                 [-A threshold [-B window] [-M tiles.u32]]   (spp is the cap; not with -c or -W)\n");
     return 2;
 }
 
@@ -90,9 +99,11 @@ bool ends_with(const std::string &s, const char *suf) {
 
 int main(int argc, char **argv) {
     std::vector<const char *> pos;
-    uint32_t depth = 50, window = 0, stop_after = 0, var_windows = 0;
+    uint32_t depth = 50, window = 0, stop_after = 0, var_windows = 0, ad_window = 0;
     uint64_t seed = 1;
-    std::string out_img = "rendered.png", out_f64, ckpt, aov, denoised, out_var;
+    double ad_threshold = 0.0;
+    bool adaptive = false, ad_window_given = false;
+    std::string out_img = "rendered.png", out_f64, ckpt, aov, denoised, out_var, out_tiles;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto val = [&](const char *name) -> const char * {
@@ -112,12 +123,24 @@ int main(int argc, char **argv) {
         else if (a == "-D") denoised = val("-D");
         else if (a == "-V") out_var = val("-V");
         else if (a == "-W") var_windows = (uint32_t)std::strtoul(val("-W"), nullptr, 10);
+        else if (a == "-A") {
+            const char *v = val("-A");
+            char *end = nullptr;
+            ad_threshold = std::strtod(v, &end);
+            if (end == v || *end) return usage();
+            adaptive = true;
+        } else if (a == "-B") {
+            ad_window = (uint32_t)std::strtoul(val("-B"), nullptr, 10);
+            ad_window_given = true;
+        } else if (a == "-M") out_tiles = val("-M");
         else if (a == "-x") stop_after = (uint32_t)std::strtoul(val("-x"), nullptr, 10);
         else if (a.size() > 1 && a[0] == '-') return usage();
         else pos.push_back(argv[i]);
     }
     if (pos.empty() || pos.size() == 3 || pos.size() > 4 || (!ckpt.empty() && window == 0)) return usage();
     if (!out_var.empty() && !ckpt.empty()) return usage();
+    if (adaptive && (!ckpt.empty() || var_windows != 0)) return usage();
+    if (!adaptive && (ad_window_given || !out_tiles.empty())) return usage();
     const uint32_t spp = pos.size() >= 2 ? (uint32_t)std::strtoul(pos[1], nullptr, 10) : 100;  // the GUI's 100
     const uint32_t w = pos.size() == 4 ? (uint32_t)std::strtoul(pos[2], nullptr, 10) : 1600;    // main.rs:26
     const uint32_t h = pos.size() == 4 ? (uint32_t)std::strtoul(pos[3], nullptr, 10) : 900;
@@ -136,7 +159,28 @@ int main(int argc, char **argv) {
     if ((rc = pt_renderer_create(scene, -1, depth, &r))) return fail("renderer", rc);
     const size_t npix = (size_t)w * h;
     std::vector<double> rgb(npix * 3), variance;
-    if (!out_var.empty()) {
+    if (adaptive) {
+        // every tile to its noise target, spp at the most; the variance plane serves -V and -D
+        const uint32_t tiles = ((w + 15) / 16) * ((h + 15) / 16);
+        std::vector<uint32_t> tile_samples(tiles);
+        uint64_t launched = 0;
+        variance.resize(npix * 3);
+        if (!ad_window_given) ad_window = PT_ADAPTIVE_WINDOW;
+        if ((rc = pt_render_adaptive(r, &cam, w, h, ad_window, 0, spp, ad_threshold, PT_ADAPTIVE_LUMINANCE_FLOOR,
+                                     PT_ADAPTIVE_MERGE_GAP, seed, rgb.data(), variance.data(), tile_samples.data(),
+                                     nullptr, &launched)))
+            return fail("adaptive render", rc);
+        std::fprintf(stderr, "pt_render: %llu of %llu pixel-samples rendered\n", (unsigned long long)launched,
+                     (unsigned long long)npix * spp);
+        if (!out_var.empty() && !write_doubles(out_var, variance)) return 1;
+        if (!out_tiles.empty()) {
+            FILE *f = std::fopen(out_tiles.c_str(), "wb");
+            if (!f || std::fwrite(tile_samples.data(), sizeof(uint32_t), tiles, f) != tiles || std::fclose(f) != 0) {
+                std::fprintf(stderr, "pt_render: cannot write %s\n", out_tiles.c_str());
+                return 1;
+            }
+        }
+    } else if (!out_var.empty()) {
         // the frame in sample windows, with the variance of each pixel's mean beside it
         variance.resize(npix * 3);
         if (var_windows == 0) var_windows = spp < 8 ? spp : 8;
