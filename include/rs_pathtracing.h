@@ -184,7 +184,14 @@ int pt_renderer_peer_access(const pt_renderer *r, int *pairs, int *enabled);
  * image: every setting renders the same bits.  pt_option_name(i) lists the
  * names (NULL past the end).  get_option also reads "bvh_nodes" (read-only:
  * nodes per octant layout of the renderer's BVH; from 32768 on, the bounce
- * runs its large-tree build, whose node slab test is f32). */
+ * runs its large-tree build, whose node slab test is f32), and what the
+ * renderer's first device launched for its last frame, set where the launch
+ * is made (read-only as well; set_option refuses the names): "ran_engine"
+ * (0 megakernel, 1 wavefront, -1 nothing launched yet or the call refused)
+ * and "ran_mega", "ran_bounce", "ran_walk", "ran_march" (-1: the frame
+ * launched none of that kernel; else the kernel build's template arguments
+ * as sum((argument + 2) << (6 * position)), in the order of pt_builds.hpp's
+ * lists of builds). */
 int pt_renderer_set_option(pt_renderer *r, const char *name, int64_t value);
 int pt_renderer_get_option(const pt_renderer *r, const char *name, int64_t *value);
 const char *pt_option_name(int index);

@@ -390,6 +390,18 @@ class HipRenderer(Renderer):
         """Every tuning knob and its current value."""
         return {n: self.get_option(n) for n in option_names()}
 
+    def last_builds(self) -> dict:
+        """What the last frame launched (the read-only "ran_*" names of pt_renderer_get_option; a renderer on several
+        devices reports its first device's): {"engine": 0 megakernel / 1 wavefront / -1 nothing, "mega": the
+        render_tiles build's template arguments (nw, waves, fk), "bounce": wf_bounce's (waves, fk, ext, bigbvh,
+        split, deep), "walk": wf_walk's (waves, qn), "march": wf_march's (fk,)}; None for a kernel the frame did not
+        launch.  fk: 0 Heart, -1 any function, -2 none."""
+        out = {"engine": self.get_option("ran_engine")}
+        for kernel, columns in BUILD_COLUMNS.items():
+            key = self.get_option("ran_" + kernel)
+            out[kernel] = None if key < 0 else tuple(((key >> (6 * j)) & 63) - 2 for j in range(columns))
+        return out
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h and _lib is not None:
@@ -669,6 +681,8 @@ def option_names() -> list:
 # the defaults (pt_builds.hpp Tuning): bench.py reports knobs that differ
 OPTION_DEFAULTS = {"engine": 0, "mega_waves": 4, "diag": 0, "wf_slots": 2, "wf_paths": 0, "wf_min_chunks": 1,
                    "wf_bounce_waves": 3, "wf_march_slice": 256, "wf_walk": 5, "bvh_leaf": 1}
+# template arguments per kernel build, in the column order of pt_builds.hpp's lists (HipRenderer.last_builds)
+BUILD_COLUMNS = {"mega": 3, "bounce": 6, "walk": 2, "march": 1}
 
 
 def shard_tiles(width: int, height: int, rank: int, world: int) -> int:

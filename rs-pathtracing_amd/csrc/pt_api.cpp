@@ -730,6 +730,8 @@ int pt_renderer_get_option(const pt_renderer *r, const char *name, int64_t *valu
         *value = r->gpus[0].ds.view.nnodes;
         return PT_OK;
     }
+    // read-only too: what device 0's last launch_render call launched (builds::Ran; set_option knows no such name)
+    if (ran_get(r->gpus[0].ws.ran, name, value)) return PT_OK;
     if (!tuning_get(r->gpus[0].ws.tune, name, value)) return fail(PT_ERR_INVALID, std::string("unknown option: ") + name);
     return PT_OK;
 }

@@ -192,6 +192,35 @@ struct Choice {
     bool ext;     // the wf_unwind / wf_reduce builds
 };
 
+// A build's template arguments in its list's column order as one number: sum((field + 2) << (6 * j)) (a field is in
+// [-2, 32]: one base-64 digit each; a bool counts as 0 or 1).  tests/test_builds.py packs its chosen sets the same way.
+constexpr int64_t key() { return 0; }
+template <class... T>
+constexpr int64_t key(int field, T... rest) {
+    return (int64_t)(field + 2) + (key(rest...) << 6);
+}
+
+// What the last launch_render call launched (WaveWorkspace::ran): written by the launchers in the branch that
+// launches, never from choose()'s output, and read through pt_renderer_get_option as "ran_engine" (0 megakernel,
+// 1 wavefront) and "ran_mega", "ran_bounce", "ran_walk", "ran_march" (the build's key; FIRST is no part of it).
+// -1: the call launched none of that kernel (ran_engine: nothing at all, e.g. a refused call).
+struct Ran {
+    int64_t engine = -1, mega = -1, bounce = -1, walk = -1, march = -1;
+};
+inline bool ran_get(const Ran &r, const char *name, int64_t *v) {
+    static constexpr struct {
+        const char *name;
+        int64_t Ran::*m;
+    } NAMES[] = {{"ran_engine", &Ran::engine}, {"ran_mega", &Ran::mega}, {"ran_bounce", &Ran::bounce},
+                 {"ran_walk", &Ran::walk}, {"ran_march", &Ran::march}};
+    for (const auto &n : NAMES)
+        if (name && !strcmp(name, n.name)) {
+            *v = r.*(n.m);
+            return true;
+        }
+    return false;
+}
+
 // knob when the builds of `set` have that budget, else the default build's
 template <int N>
 inline int budget(const int (&set)[N], int knob, int dflt) {

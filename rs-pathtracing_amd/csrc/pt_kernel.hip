@@ -251,6 +251,7 @@ hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P, double
                               WaveWorkspace *ws, const builds::Choice &ch);
 
 hipError_t launch_render(const DeviceScene &s, const FrameParams &P, double *out, hipStream_t st, WaveWorkspace &ws) {
+    ws.ran = builds::Ran{};  // what this call launches: set below and in launch_render_wave, where a launch is made
     if (P.tile_count == 0) return hipSuccess;
     ws.refusal[0] = 0;
     builds::Inputs in{};
@@ -276,6 +277,8 @@ hipError_t launch_render(const DeviceScene &s, const FrameParams &P, double *out
 #define X(NW, WAVES, FK)                                                             \
     if (ch.mega.is(NW, WAVES, FK)) {                                                 \
         render_tiles<NW, WAVES, FK><<<P.tile_count, 256, 0, st>>>(s.view, P, out);   \
+        ws.ran.engine = builds::MEGA;                                                \
+        ws.ran.mega = builds::key(NW, WAVES, FK);                                    \
         launched = true;                                                             \
     }
     PT_MEGA_BUILDS(X)

@@ -61,6 +61,8 @@ struct WaveWorkspace {
     // why launch_render refused the last frame without a HIP failure (empty: it did not): a frame whose workspace
     // the device cannot hold (pt_wave.hip launch_render_wave)
     char refusal[320] = {};
+    // the engine and the kernel builds the last launch_render call launched (pt_renderer_get_option "ran_*")
+    builds::Ran ran;
 };
 void wave_workspace_free(WaveWorkspace *ws);
 

@@ -1237,10 +1237,12 @@ static uint32_t march_grid() {
 // The bounce of iteration it: the chunk's camera rays (FIRST), or the live list of it.
 template <bool FIRST>
 static hipError_t run_bounce(const builds::Bounce &b, uint32_t blocks, hipStream_t st, const WfArgs *A, int it,
-                             unsigned long long *diag) {
+                             unsigned long long *diag, builds::Ran *ran) {
 #define X(WAVES, FK, EXT, BIGBVH, SPLIT, DEEP)                                                       \
     if (b.is(WAVES, FK, EXT, BIGBVH, SPLIT, DEEP)) {                                                 \
         wf_bounce<FIRST, WAVES, FK, EXT, BIGBVH, SPLIT, DEEP><<<blocks, 256, 0, st>>>(A, it, diag); \
+        ran->engine = builds::WAVE;                                                                  \
+        ran->bounce = builds::key(WAVES, FK, EXT, BIGBVH, SPLIT, DEEP);                              \
         return hipSuccess;                                                                           \
     }
     PT_BOUNCE_BUILDS(X)
@@ -1249,10 +1251,12 @@ static hipError_t run_bounce(const builds::Bounce &b, uint32_t blocks, hipStream
 }
 
 // The new rays' BVH walk, over the live list of it + 1 (builds::Walk::on).
-static hipError_t run_walk(const builds::Walk &w, uint32_t blocks, hipStream_t st, const WfArgs *A, int it) {
+static hipError_t run_walk(const builds::Walk &w, uint32_t blocks, hipStream_t st, const WfArgs *A, int it,
+                           builds::Ran *ran) {
 #define X(WAVES, QN)                                      \
     if (w.is(WAVES, QN)) {                                \
         wf_walk<WAVES, QN><<<blocks, 256, 0, st>>>(A, it); \
+        ran->walk = builds::key(WAVES, QN);               \
         return hipSuccess;                                \
     }
     PT_WALK_BUILDS(X)
@@ -1262,11 +1266,12 @@ static hipError_t run_walk(const builds::Walk &w, uint32_t blocks, hipStream_t s
 
 // The march queue of iteration it, on the persistent grid.
 static hipError_t run_march(const builds::March &m, hipStream_t st, const WfArgs *A, int it,
-                            unsigned long long *diag, uint32_t slice) {
+                            unsigned long long *diag, uint32_t slice, builds::Ran *ran) {
     const uint32_t blocks = march_grid();
 #define X(FK)                                                        \
     if (m.is(FK)) {                                                  \
         wf_march<FK><<<blocks, 256, 0, st>>>(A, it, diag, slice); \
+        ran->march = builds::key(FK);                                \
         return hipSuccess;                                           \
     }
     PT_MARCH_BUILDS(X)
@@ -1478,8 +1483,9 @@ hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
                 if (bb > WF_BOUNCE_CAP) bb = WF_BOUNCE_CAP;
                 // iteration 0: slots [0, paths) are the chunk's camera rays
                 e = timed(ws->timer, cs, K_BOUNCE, [&] {
-                    return it == 0 ? run_bounce<true>(bc.bounce, (paths + 255) / 256, cs, A, it, bounce_diag)
-                                   : run_bounce<false>(bc.bounce, bb, cs, A, it, bounce_diag);
+                    builds::Ran *ran = &ws->ran;
+                    return it == 0 ? run_bounce<true>(bc.bounce, (paths + 255) / 256, cs, A, it, bounce_diag, ran)
+                                   : run_bounce<false>(bc.bounce, bb, cs, A, it, bounce_diag, ran);
                 });
                 if (e != hipSuccess) return e;
                 if (it == iters - 1) continue;  // the last bounce only shades
@@ -1499,12 +1505,12 @@ hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
                 });
                 if (e != hipSuccess) return e;
                 if (bc.walk.on) {
-                    e = timed(ws->timer, cs, K_WALK, [&] { return run_walk(bc.walk, bb, cs, A, it); });
+                    e = timed(ws->timer, cs, K_WALK, [&] { return run_walk(bc.walk, bb, cs, A, it, &ws->ran); });
                     if (e != hipSuccess) return e;
                 }
                 if (!bc.march.on) continue;  // no ray-marched shape: the march queue is always empty
                 e = timed(ws->timer, cs, K_MARCH,
-                          [&] { return run_march(bc.march, cs, A, it, march_diag, march_slice); });
+                          [&] { return run_march(bc.march, cs, A, it, march_diag, march_slice, &ws->ran); });
                 if (e != hipSuccess) return e;
             }
         }

@@ -58,6 +58,28 @@ int builds_list(int which, int64_t *out) {
     return n;
 }
 
+// The record of what a frame launched (builds::Ran, builds::key).  ran_keys: builds::key of every instantiated build
+// of kernel `which`, in list order (the expression the launchers record); returns how many.  One Ran, empty after
+// ran_reset: ran_note writes a field as the launchers do (0 engine, 1 mega, 2 bounce, 3 walk, 4 march), ran_read
+// is ran_get (0: no such name; *v is then untouched).
+int ran_keys(int which, int64_t *out) {
+    int n = 0;
+#define KEY(...) out[n++] = key(__VA_ARGS__);
+    if (which == 0) { PT_MEGA_BUILDS(KEY) }
+    if (which == 1) { PT_BOUNCE_BUILDS(KEY) }
+    if (which == 2) { PT_WALK_BUILDS(KEY) }
+    if (which == 3) { PT_MARCH_BUILDS(KEY) }
+#undef KEY
+    return n;
+}
+static Ran g_ran;
+void ran_reset() { g_ran = Ran{}; }
+void ran_note(int field, int64_t v) {
+    int64_t Ran::*const m[] = {&Ran::engine, &Ran::mega, &Ran::bounce, &Ran::walk, &Ran::march};
+    g_ran.*(m[field]) = v;
+}
+int ran_read(const char *name, int64_t *v) { return ran_get(g_ran, name, v) ? 1 : 0; }
+
 // The knob table: names in the API's order, and a row's range, set (up to 8 values) and zero rule.
 int knob_count() { return KNOB_COUNT; }
 const char *knob_name(int k) { return k >= 0 && k < KNOB_COUNT ? KNOBS[k].name : nullptr; }

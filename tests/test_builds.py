@@ -166,6 +166,51 @@ def test_choice_over_the_whole_input_space(L):
         assert set(entries) <= chosen[k], "%s: instantiated but never chosen: %s" % (k, set(entries) - chosen[k])
 
 
+def test_record_of_launched_builds(L):
+    """builds::Ran, what a frame reports it launched (pt_renderer_get_option "ran_*"; the device side is
+    tests/test_gpu_builds.py): builds::key packs every instantiated build as `chosen` is packed above, so that
+    HipRenderer.last_builds unpacks the list's own row; an empty record reads -1 everywhere; the names are read-only
+    (no knob is called so) and nothing else is a name."""
+    i64p = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
+    L.ran_keys.argtypes = [C.c_int, i64p]
+    L.ran_note.argtypes = [C.c_int, C.c_int64]
+    L.ran_read.argtypes = [C.c_char_p, C.POINTER(C.c_int64)]
+    names = ("ran_engine", "ran_mega", "ran_bounce", "ran_walk", "ran_march")
+
+    def read(name):
+        v = C.c_int64(-77)
+        ok = L.ran_read(name.encode() if name is not None else None, C.byref(v))
+        return ok, v.value
+
+    L.ran_reset()
+    assert [read(n) for n in names] == [(1, -1)] * 5
+    for name in ("ran", "ran_", "ran_engine ", "ran_first", "engine", "bvh_nodes", "", None):
+        assert read(name) == (0, -77), name
+    pt = __import__("conftest").load_package()  # (importing the mirror loads no library)
+    assert list(pt.BUILD_COLUMNS.items()) == [(k, len(cols)) for k, (_, cols) in LISTS.items()]
+    seen = set()
+    for k, (which, cols) in LISTS.items():
+        entries = build_list(L, which, len(cols))
+        keys = np.full(len(entries) + 1, -5, dtype=np.int64)
+        assert L.ran_keys(which, keys) == len(entries) and keys[-1] == -5
+        for entry, key in zip(entries, keys.tolist()):
+            assert key == sum((f + 2) << (6 * j) for j, f in enumerate(entry)) and key >= 0, (k, entry)
+            assert tuple(((key >> (6 * j)) & 63) - 2 for j in range(len(cols))) == entry  # last_builds' unpacking
+            L.ran_note(1 + which, key)
+            assert read("ran_" + k) == (1, key)
+            seen.add((k, key))
+        assert len({key for kk, key in seen if kk == k}) == len(entries)  # no two builds share a key
+    for engine in (MEGA, WAVE):
+        L.ran_note(0, engine)
+        assert read("ran_engine") == (1, engine)
+    L.ran_reset()
+    assert [read(n) for n in names] == [(1, -1)] * 5
+    # read-only: no knob has such a name, so tuning_set, which is all pt_renderer_set_option has, refuses them
+    for n in names:
+        assert L.knobs_set(n.encode(), 0) == 0 and L.knobs_get(n.encode(), C.byref(C.c_int64())) == 0
+        assert n not in [L.knob_name(k).decode() for k in range(L.knob_count())]
+
+
 # The options in the order the API reports them and their legal values: TUNING_NAMES, tuning_field and tuning_set of
 # commit 7d8f969 (pt_kernel.hip:301-351).  A range is (lo, hi); wf_paths also takes 0.
 KNOBS = [("engine", (0, 2)), ("mega_waves", (2, 5)), ("diag", (0, 1)), ("wf_slots", (1, 4)),

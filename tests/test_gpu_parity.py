@@ -112,6 +112,11 @@ def test_cornell_partial_tiles_and_odd_size(pt, cornell):
 
 
 def test_spheres_frame_gui_depth(pt, spheres):
+    """spheres.json at the bins' depth 50 on the default engine, which is the wavefront one (the scene marches two
+    Hearts), so no register stack runs here.  It checks that a frame of 52 iterations per chunk is the oracle's; it
+    does not check the id stacks' deep levels: on the oracle 5 of the 1296 pixels differ between depth 8 and 16,
+    none between 16 and 32 and one between 32 and 50 (paths under the open sky end long before), so a stack that
+    lost every id past its 16th would change one pixel.  tests/test_gpu_stacks.py has the frames that read them."""
     img, ref = render_pair(pt, spheres, 48, 27, 3, 50, seed=2)  # depth 50 = the bins' depth
     check_image(img, ref)
 
@@ -265,7 +270,11 @@ def test_wavefront_launches_follow_the_plan(pt, cornell):
 
 
 def test_wavefront_deep_paths(pt, spheres, cornell):
-    """Depth 50 (the bins' depth) through the wavefront engine: 32-word stacks."""
+    """Depths 50 (the bins' depth) and 20 through the wavefront engine: 52 and 22 iterations per chunk, the id stacks
+    in memory.  The spheres frame does not read the stacks' deep levels: on the oracle 5 of its 960 pixels differ
+    between depth 8 and 16 and none between 16 and 64, so ids past the 16th could hold anything.  The cornell frame
+    (a closed box) reads levels 9 to 20: 107 of its 384 pixels differ between depth 8 and 16, 21 between 16 and 20.
+    tests/test_gpu_stacks.py has the frames that read every level up to 64."""
     img, ref = render_pair(pt, spheres, 40, 24, 2, 50, seed=6, engine=2)
     check_image(img, ref)
     img, ref = render_pair(pt, cornell, 24, 16, 2, 20, seed=6, engine=2)
