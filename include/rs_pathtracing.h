@@ -429,6 +429,25 @@ int pt_render_adaptive(pt_renderer *r, const pt_camera *camera, uint32_t width, 
                        uint32_t min_samples, uint32_t max_samples, double threshold, double luminance_floor,
                        uint32_t merge_gap, uint64_t seed, double *rgb, double *variance, uint32_t *tile_samples,
                        double *tile_error, uint64_t *samples_rendered);
+/* The same frame with each window rendered in ONE launch over the list of the
+ * still-active tiles (pt_render_device_tiles) instead of one launch per run:
+ * pt_render_adaptive_device's parameters without merge_gap.  d_out,
+ * d_variance, d_tile_samples and d_tile_error are bit for bit those of
+ * pt_render_adaptive_device (the frame never depended on merge_gap);
+ * samples_rendered is exactly the sum over the tiles of pixels * tile_samples:
+ * no stopped tile is rendered again.  The same errors, the same blocking once
+ * per window, the same workspace (the list is kept by the renderer, not in
+ * d_work).  (Library 0.4.3; no ABI change.) */
+int pt_render_adaptive_list_device(pt_renderer *r, const pt_camera *camera, uint32_t width, uint32_t height,
+                                   uint32_t window, uint32_t min_samples, uint32_t max_samples, double threshold,
+                                   double luminance_floor, uint64_t seed, uint32_t rank, uint32_t world,
+                                   double *d_out, double *d_variance, uint32_t *d_tile_samples, double *d_tile_error,
+                                   double *d_work, void *hip_stream, uint64_t *samples_rendered);
+/* the same into host buffers (world 1); allocates, copies, blocks */
+int pt_render_adaptive_list(pt_renderer *r, const pt_camera *camera, uint32_t width, uint32_t height,
+                            uint32_t window, uint32_t min_samples, uint32_t max_samples, double threshold,
+                            double luminance_floor, uint64_t seed, double *rgb, double *variance,
+                            uint32_t *tile_samples, double *tile_error, uint64_t *samples_rendered);
 
 /* ---- resumable frames (checkpoint / resume) ----------------------------- */
 /* The reference renders a frame in one go and keeps nothing between runs
@@ -447,6 +466,24 @@ int pt_render_adaptive(pt_renderer *r, const pt_camera *camera, uint32_t width, 
 int pt_render_device_samples(pt_renderer *r, const pt_camera *camera, uint32_t width, uint32_t height,
                              uint32_t samples_number, uint64_t seed, uint32_t rank, uint32_t world,
                              uint32_t s_begin, uint32_t s_end, double *d_out, void *hip_stream);
+/* pt_render_device_samples restricted to a list of tiles: `tiles` (a host
+ * array, copied before the call returns) holds tile_count >= 1 strictly
+ * ascending indices into the rank's tile list, each below
+ * pt_shard_tiles(width, height, rank, world).  The listed tiles' elements of
+ * d_out are read (s_begin > 0) and written exactly as
+ * pt_render_device_samples reads and writes them, bit for bit, a listed
+ * partial tile's shard padding included; every other element of d_out is
+ * neither read nor written.  One launch sequence whatever the list's gaps, so
+ * a caller that renders few tiles of a frame (adaptive sampling, a region of
+ * interest, a repaired tile) pays for those tiles alone.  PT_ERR_INVALID,
+ * writing nothing: pt_render_device_samples' own argument errors, a NULL
+ * `tiles`, tile_count 0, an entry out of range or not above the entry before
+ * it.  PT_ERR_STATE while a pt_render_start frame is in flight.  Always runs
+ * the wavefront engine.  (Library 0.4.3; no ABI change.) */
+int pt_render_device_tiles(pt_renderer *r, const pt_camera *camera, uint32_t width, uint32_t height,
+                           uint32_t samples_number, uint64_t seed, uint32_t rank, uint32_t world,
+                           uint32_t s_begin, uint32_t s_end, const uint32_t *tiles, uint32_t tile_count,
+                           double *d_out, void *hip_stream);
 /* A checkpoint file: the 8 bytes "PTCKPT01", this header, `count` doubles
  * (the running sums of one rank's d_out after samples [0, samples_done)) and
  * a 64-bit FNV-1a checksum over the preceding bytes taken as little-endian

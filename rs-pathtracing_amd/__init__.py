@@ -55,6 +55,7 @@ EXPORTS = [
     "pt_variance_workspace_doubles", "pt_variance_window_device", "pt_render_variance_device", "pt_render_variance",
     "pt_denoise_variance_device", "pt_denoise_variance",
     "pt_adaptive_workspace_doubles", "pt_render_adaptive_device", "pt_render_adaptive",
+    "pt_render_device_tiles", "pt_render_adaptive_list_device", "pt_render_adaptive_list",
 ]
 ADAPTIVE_WINDOW = 8  # the recommended defaults of pt_render_adaptive (rs_pathtracing.h)
 ADAPTIVE_FLOOR = 0.01
@@ -185,6 +186,13 @@ def lib():
                                                 C.POINTER(u64)]),
         "pt_render_adaptive": (C.c_int, [vp, C.POINTER(CameraStruct), u32, u32, u32, u32, u32, C.c_double, C.c_double,
                                          u32, u64, d, d, C.POINTER(u32), d, C.POINTER(u64)]),
+        "pt_render_device_tiles": (C.c_int, [vp, C.POINTER(CameraStruct), u32, u32, u32, u64, u32, u32, u32, u32,
+                                             C.POINTER(u32), u32, vp, vp]),
+        "pt_render_adaptive_list_device": (C.c_int, [vp, C.POINTER(CameraStruct), u32, u32, u32, u32, u32, C.c_double,
+                                                     C.c_double, u64, u32, u32, vp, vp, vp, vp, vp, vp,
+                                                     C.POINTER(u64)]),
+        "pt_render_adaptive_list": (C.c_int, [vp, C.POINTER(CameraStruct), u32, u32, u32, u32, u32, C.c_double,
+                                              C.c_double, u64, d, d, C.POINTER(u32), d, C.POINTER(u64)]),
         "pt_checkpoint_save": (C.c_int, [C.c_char_p, C.POINTER(CheckpointStruct), d]),
         "pt_checkpoint_load": (C.c_int, [C.c_char_p, C.POINTER(CheckpointStruct), d, u64]),
         "pt_shard_tiles": (u32, [u32, u32, u32, u32]),
@@ -460,6 +468,19 @@ class HipRenderer(Renderer):
                                               int(s_begin), int(s_end), C.c_void_p(out_ptr),
                                               C.c_void_p(stream_ptr)))
 
+    def render_device_tiles(self, camera: Camera, width: int, height: int, spp: int, seed: int, rank: int,
+                            world: int, s_begin: int, s_end: int, tiles, out_ptr: int, stream_ptr: int = 0):
+        """render_device_samples restricted to `tiles`: strictly ascending indices into the rank's tile list.
+        The listed tiles end bit for bit as render_device_samples leaves them; nothing else at out_ptr is read or
+        written (pt_render_device_tiles)."""
+        t = np.ascontiguousarray(np.asarray(tiles, dtype=np.int64).reshape(-1))
+        if t.size and (t.min() < 0 or t.max() > 0xFFFFFFFF):
+            raise ValueError("tiles must be unsigned 32-bit tile indices")
+        t = t.astype(np.uint32)
+        _check(lib().pt_render_device_tiles(self._h, C.byref(camera._c), width, height, spp, seed, rank, world,
+                                            int(s_begin), int(s_end), t.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                            int(t.size), C.c_void_p(out_ptr), C.c_void_p(stream_ptr)))
+
     def render_frame_device(self, camera: Camera, width: int, height: int, spp: int, seed: int, frame_ptr: int,
                             stream_ptr: int = 0):
         """The whole frame over all of the renderer's devices into device memory at frame_ptr (first
@@ -522,22 +543,28 @@ class HipRenderer(Renderer):
     # ---- adaptive sampling: every tile stops at a noise target (pt_render_adaptive) ----
     def render_adaptive(self, camera: Camera, img_params: ImageParams, max_samples: int, threshold: float,
                         window: int = ADAPTIVE_WINDOW, min_samples: int = 0, luminance_floor: float = ADAPTIVE_FLOOR,
-                        merge_gap: int = ADAPTIVE_MERGE_GAP, seed=None, return_samples_rendered: bool = False):
+                        merge_gap: int = ADAPTIVE_MERGE_GAP, seed=None, return_samples_rendered: bool = False,
+                        tile_list: bool = False):
         """(rgb, tile_samples, tile_error, variance): the frame rendered in windows of `window` samples, every
         16x16 tile stopped once the relative standard error of its luminance is at most `threshold` (or at
         max_samples).  rgb and variance are (w*h, 3) float64; tile_samples (uint32) and tile_error (float64, the
         squared relative standard error at the stop) have one entry per tile, row-major.  A tile's pixels are
-        render(camera, img_params, tile_samples[tile], seed)'s, bit for bit.  See pt_render_adaptive."""
+        render(camera, img_params, tile_samples[tile], seed)'s, bit for bit.  tile_list: every window is one launch
+        over the list of the still-active tiles (merge_gap is not used); the outputs are the same bits.  See
+        pt_render_adaptive and pt_render_adaptive_list."""
         s = self.seed if seed is None else int(seed)
         w, h = img_params.width, img_params.height
         n, nt = w * h, ((w + 15) // 16) * ((h + 15) // 16)
         rgb, var = np.zeros((n, 3), dtype=np.float64), np.zeros((n, 3), dtype=np.float64)
         ts, te = np.zeros(nt, dtype=np.uint32), np.zeros(nt, dtype=np.float64)
         launched = C.c_uint64(0)
-        _check(lib().pt_render_adaptive(self._h, C.byref(camera._c), w, h, int(window), int(min_samples),
-                                        int(max_samples), float(threshold), float(luminance_floor), int(merge_gap),
-                                        s, _dptr(rgb), _dptr(var), ts.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                        _dptr(te), C.byref(launched)))
+        head = (self._h, C.byref(camera._c), w, h, int(window), int(min_samples), int(max_samples), float(threshold),
+                float(luminance_floor))
+        tail = (s, _dptr(rgb), _dptr(var), ts.ctypes.data_as(C.POINTER(C.c_uint32)), _dptr(te), C.byref(launched))
+        if tile_list:
+            _check(lib().pt_render_adaptive_list(*head, *tail))
+        else:
+            _check(lib().pt_render_adaptive(*head, int(merge_gap), *tail))
         if return_samples_rendered:
             return rgb, ts, te, var, int(launched.value)
         return rgb, ts, te, var
@@ -546,19 +573,22 @@ class HipRenderer(Renderer):
                                seed: int, rank: int, world: int, out_ptr: int, variance_ptr: int,
                                tile_samples_ptr: int, tile_error_ptr: int, work_ptr: int, stream_ptr: int = 0,
                                window: int = ADAPTIVE_WINDOW, min_samples: int = 0,
-                               luminance_floor: float = ADAPTIVE_FLOOR, merge_gap: int = ADAPTIVE_MERGE_GAP) -> int:
+                               luminance_floor: float = ADAPTIVE_FLOOR, merge_gap: int = ADAPTIVE_MERGE_GAP,
+                               tile_list: bool = False) -> int:
         """render_adaptive into device buffers of the caller's, render_device's layout (variance_ptr and
         tile_error_ptr may be 0), with adaptive_workspace_doubles(width, height, rank, world) doubles at work_ptr;
         blocks, synchronising stream_ptr once per window.  Returns the pixel-samples launched
-        (pt_render_adaptive_device)."""
+        (pt_render_adaptive_device; tile_list: pt_render_adaptive_list_device, one launch per window)."""
         launched = C.c_uint64(0)
-        _check(lib().pt_render_adaptive_device(self._h, C.byref(camera._c), width, height, int(window),
-                                               int(min_samples), int(max_samples), float(threshold),
-                                               float(luminance_floor), int(merge_gap), seed, rank, world,
-                                               C.c_void_p(out_ptr or None), C.c_void_p(variance_ptr or None),
-                                               C.c_void_p(tile_samples_ptr or None),
-                                               C.c_void_p(tile_error_ptr or None), C.c_void_p(work_ptr or None),
-                                               C.c_void_p(stream_ptr), C.byref(launched)))
+        head = (self._h, C.byref(camera._c), width, height, int(window), int(min_samples), int(max_samples),
+                float(threshold), float(luminance_floor))
+        tail = (seed, rank, world, C.c_void_p(out_ptr or None), C.c_void_p(variance_ptr or None),
+                C.c_void_p(tile_samples_ptr or None), C.c_void_p(tile_error_ptr or None),
+                C.c_void_p(work_ptr or None), C.c_void_p(stream_ptr), C.byref(launched))
+        if tile_list:
+            _check(lib().pt_render_adaptive_list_device(*head, *tail))
+        else:
+            _check(lib().pt_render_adaptive_device(*head, int(merge_gap), *tail))
         return int(launched.value)
 
     # ---- probes --------------------------------------------------------

@@ -1,8 +1,9 @@
 // pt_adaptive.hpp — adaptive sampling at the granularity of the 16x16 tile: a frame is rendered in
 // sample windows, and after each window every tile that is still active is judged by the relative standard error of
 // its luminance, estimated by batch means from the windows' running sums (§3.9's estimate); a tile that meets the
-// target, or reaches the cap, is divided out into the frame and never touched again.  No render kernel changes: the
-// windows go through launch_render over tile ranges into a sums plane, and this pass runs on that plane.  f64, one
+// target, or reaches the cap, is divided out into the frame and never touched again.  The windows go through
+// launch_render into a sums plane -- over ranges of the tile list (adaptive_runs), or over the list of the active tiles
+// in one launch (adaptive_list) -- and this pass runs on that plane.  f64, one
 // fixed order of operations, no transcendental function, so the GPU, the host build (tests/native/adaptive.mk) and
 // the numpy restatement (tests/adaptiveref.py) give the same bits.
 //
@@ -171,6 +172,23 @@ inline std::vector<AdaptiveRun> adaptive_runs(const uint8_t *active, uint32_t nt
             runs.push_back(AdaptiveRun{i, 1});
     }
     return runs;
+}
+
+// A listed launch's tiles (launch_render's `tiles`): n >= 1 entries of the rank's tile list, strictly
+// ascending (so distinct: two chunks never write one pixel) and each below ntiles.
+inline bool tile_list_ok(const uint32_t *list, size_t n, uint32_t ntiles) {
+    if (!list || n < 1) return false;
+    for (size_t i = 0; i < n; i++)
+        if (list[i] >= ntiles || (i > 0 && list[i] <= list[i - 1])) return false;
+    return true;
+}
+
+// The window's one listed launch: the active tiles, ascending.
+inline std::vector<uint32_t> adaptive_list(const uint8_t *active, uint32_t ntiles) {
+    std::vector<uint32_t> list;
+    for (uint32_t i = 0; i < ntiles; i++)
+        if (active[i]) list.push_back(i);
+    return list;
 }
 
 // One window's pass over the `ntiles` tiles of the rank's list, queued on st: one launch of one 256-thread block per

@@ -451,8 +451,9 @@ void rank_range(uint32_t a, uint32_t b, uint32_t rank, uint32_t world, uint32_t 
 
 // launch_render on g's device: a refusal (WaveWorkspace::refusal: a deep frame whose workspace does not fit) is
 // PT_ERR_UNSUPPORTED with its message, anything else a HIP failure.
-int render_on(GpuShare &g, const FrameParams &P, double *dst, hipStream_t st) {
-    const hipError_t e = launch_render(g.ds, P, dst, st, g.ws);
+// tiles: a listed launch (launch_render).
+int render_on(GpuShare &g, const FrameParams &P, double *dst, hipStream_t st, const uint32_t *tiles = nullptr) {
+    const hipError_t e = launch_render(g.ds, P, dst, st, g.ws, tiles);
     if (e == hipSuccess) return PT_OK;
     if (g.ws.refusal[0]) return fail(PT_ERR_UNSUPPORTED, g.ws.refusal);
     return hip_fail(e, "launch_render");
@@ -925,6 +926,30 @@ int pt_render_device_samples(pt_renderer *r, const pt_camera *cam, uint32_t w, u
     return PT_OK;
 }
 
+int pt_render_device_tiles(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
+                           uint32_t rank, uint32_t world, uint32_t s_begin, uint32_t s_end, const uint32_t *tiles,
+                           uint32_t tile_count, double *d_out, void *stream) {
+    if (!r || !cam || !d_out || !tiles) return fail(PT_ERR_INVALID, "null argument");
+    if (w == 0 || h == 0 || spp == 0) return fail(PT_ERR_INVALID, "width, height and samples_number must be > 0");
+    if (world == 0 || rank >= world) return fail(PT_ERR_INVALID, "rank must be < world");
+    if (s_begin >= s_end || s_end > spp)
+        return fail(PT_ERR_INVALID, "sample window must satisfy 0 <= s_begin < s_end <= samples_number");
+    if (!tile_list_ok(tiles, tile_count, pt_shard_tiles(w, h, rank, world)))
+        return fail(PT_ERR_INVALID, "tiles must be 1 or more strictly ascending entries of the rank's tile list");
+    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
+    GpuShare &g = r->gpus[0];
+    HIP_TRY(hipSetDevice(g.device));
+    FrameParams P = frame_params(r, *cam, w, h, spp, seed);
+    P.rank = rank;
+    P.world = world;
+    P.compact = world > 1 ? 1 : 0;
+    P.tile_begin = 0;
+    P.tile_count = tile_count;  // positions of the list, which launch_render copies before it returns
+    P.s_begin = s_begin;
+    P.s_end = s_end;
+    return render_on(g, P, d_out, (hipStream_t)stream, tiles);
+}
+
 int pt_render_frame_device(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
                            double *d_frame, void *stream) {
     if (!r || !cam || !d_frame) return fail(PT_ERR_INVALID, "null argument");
@@ -1227,11 +1252,14 @@ size_t pt_adaptive_workspace_doubles(uint32_t w, uint32_t h, uint32_t rank, uint
     return adaptive_workspace_doubles(variance_count(w, h, rank, world));
 }
 
-int pt_render_adaptive_device(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t window,
-                              uint32_t min_samples, uint32_t max_samples, double threshold, double luminance_floor,
-                              uint32_t merge_gap, uint64_t seed, uint32_t rank, uint32_t world, double *d_out,
-                              double *d_variance, uint32_t *d_tile_samples, double *d_tile_error, double *d_work,
-                              void *stream, uint64_t *samples_rendered) {
+namespace {
+// The adaptive frame on the device, for the run-based and the listed entries: they differ only in how a window's
+// still-active tiles are launched (listed: one launch over adaptive_list; else one per run of adaptive_runs).
+int adaptive_device(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t window,
+                    uint32_t min_samples, uint32_t max_samples, double threshold, double luminance_floor,
+                    bool listed, uint32_t merge_gap, uint64_t seed, uint32_t rank, uint32_t world, double *d_out,
+                    double *d_variance, uint32_t *d_tile_samples, double *d_tile_error, double *d_work,
+                    void *stream, uint64_t *samples_rendered) {
     if (int rc = adaptive_refused(r, cam, w, h, window, min_samples, max_samples, threshold, luminance_floor, rank,
                                   world, d_out, d_tile_samples))
         return rc;
@@ -1260,9 +1288,19 @@ int pt_render_adaptive_device(pt_renderer *r, const pt_camera *cam, uint32_t w, 
         const dev::AdaptiveConsts c = adaptive_consts(k, window, min_samples, max_samples, threshold, luminance_floor);
         P.s_begin = adaptive_edge(k - 1, window, max_samples);
         P.s_end = c.e_k;
-        // the window's samples of the still-active tiles, into the sums plane: one launch per run
-        const std::vector<AdaptiveRun> runs = adaptive_runs(active.data(), ntiles, merge_gap);
-        if (runs.empty()) break;
+        // the window's samples of the still-active tiles, into the sums plane: one listed launch, or one launch per run
+        std::vector<AdaptiveRun> runs;
+        if (listed) {
+            const std::vector<uint32_t> list = adaptive_list(active.data(), ntiles);
+            if (list.empty()) break;
+            P.tile_begin = 0;
+            P.tile_count = (uint32_t)list.size();
+            if (int rc = render_on(g, P, d_work, st, list.data())) return rc;
+            for (uint32_t i : list) launched += (uint64_t)pixels[i] * (P.s_end - P.s_begin);
+        } else {
+            runs = adaptive_runs(active.data(), ntiles, merge_gap);
+            if (runs.empty()) break;
+        }
         for (const AdaptiveRun &run : runs) {
             P.tile_begin = run.begin;
             P.tile_count = run.count;
@@ -1284,10 +1322,11 @@ int pt_render_adaptive_device(pt_renderer *r, const pt_camera *cam, uint32_t w, 
     return PT_OK;
 }
 
-int pt_render_adaptive(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t window,
-                       uint32_t min_samples, uint32_t max_samples, double threshold, double luminance_floor,
-                       uint32_t merge_gap, uint64_t seed, double *rgb, double *variance, uint32_t *tile_samples,
-                       double *tile_error, uint64_t *samples_rendered) {
+// The host form: staging buffers around adaptive_device.
+int adaptive_host(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t window, uint32_t min_samples,
+                  uint32_t max_samples, double threshold, double luminance_floor, bool listed, uint32_t merge_gap,
+                  uint64_t seed, double *rgb, double *variance, uint32_t *tile_samples, double *tile_error,
+                  uint64_t *samples_rendered) {
     if (int rc = adaptive_refused(r, cam, w, h, window, min_samples, max_samples, threshold, luminance_floor, 0, 1,
                                   rgb, tile_samples))
         return rc;
@@ -1302,9 +1341,8 @@ int pt_render_adaptive(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_
     HIP_TRY(ts.alloc(ntiles));
     HIP_TRY(work.alloc(adaptive_workspace_doubles(count)));
     uint64_t launched = 0;
-    if (int rc = pt_render_adaptive_device(r, cam, w, h, window, min_samples, max_samples, threshold, luminance_floor,
-                                           merge_gap, seed, 0, 1, out.p, var.p, ts.p, err.p, work.p, r->stream(),
-                                           &launched))
+    if (int rc = adaptive_device(r, cam, w, h, window, min_samples, max_samples, threshold, luminance_floor, listed,
+                                 merge_gap, seed, 0, 1, out.p, var.p, ts.p, err.p, work.p, r->stream(), &launched))
         return rc;
     HIP_TRY(hipMemcpy(rgb, out.p, count * sizeof(double), hipMemcpyDeviceToHost));
     if (variance) HIP_TRY(hipMemcpy(variance, var.p, count * sizeof(double), hipMemcpyDeviceToHost));
@@ -1312,6 +1350,43 @@ int pt_render_adaptive(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_
     if (tile_error) HIP_TRY(hipMemcpy(tile_error, err.p, ntiles * sizeof(double), hipMemcpyDeviceToHost));
     if (samples_rendered) *samples_rendered = launched;
     return PT_OK;
+}
+}  // namespace
+
+int pt_render_adaptive_device(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t window,
+                              uint32_t min_samples, uint32_t max_samples, double threshold, double luminance_floor,
+                              uint32_t merge_gap, uint64_t seed, uint32_t rank, uint32_t world, double *d_out,
+                              double *d_variance, uint32_t *d_tile_samples, double *d_tile_error, double *d_work,
+                              void *stream, uint64_t *samples_rendered) {
+    return adaptive_device(r, cam, w, h, window, min_samples, max_samples, threshold, luminance_floor, false, merge_gap,
+                           seed, rank, world, d_out, d_variance, d_tile_samples, d_tile_error, d_work, stream,
+                           samples_rendered);
+}
+
+int pt_render_adaptive(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t window,
+                       uint32_t min_samples, uint32_t max_samples, double threshold, double luminance_floor,
+                       uint32_t merge_gap, uint64_t seed, double *rgb, double *variance, uint32_t *tile_samples,
+                       double *tile_error, uint64_t *samples_rendered) {
+    return adaptive_host(r, cam, w, h, window, min_samples, max_samples, threshold, luminance_floor, false, merge_gap,
+                         seed, rgb, variance, tile_samples, tile_error, samples_rendered);
+}
+
+int pt_render_adaptive_list_device(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t window,
+                                   uint32_t min_samples, uint32_t max_samples, double threshold,
+                                   double luminance_floor, uint64_t seed, uint32_t rank, uint32_t world, double *d_out,
+                                   double *d_variance, uint32_t *d_tile_samples, double *d_tile_error, double *d_work,
+                                   void *stream, uint64_t *samples_rendered) {
+    return adaptive_device(r, cam, w, h, window, min_samples, max_samples, threshold, luminance_floor, true, 0, seed,
+                           rank, world, d_out, d_variance, d_tile_samples, d_tile_error, d_work, stream,
+                           samples_rendered);
+}
+
+int pt_render_adaptive_list(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t window,
+                            uint32_t min_samples, uint32_t max_samples, double threshold, double luminance_floor,
+                            uint64_t seed, double *rgb, double *variance, uint32_t *tile_samples, double *tile_error,
+                            uint64_t *samples_rendered) {
+    return adaptive_host(r, cam, w, h, window, min_samples, max_samples, threshold, luminance_floor, true, 0, seed, rgb,
+                         variance, tile_samples, tile_error, samples_rendered);
 }
 
 // ---------------------------------------------------------------- probes

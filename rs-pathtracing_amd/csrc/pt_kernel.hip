@@ -248,9 +248,10 @@ __global__ __launch_bounds__(256, 2) void render_tiles_timed(dev::Scene sc, Fram
     }
 
 hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P, double *out, hipStream_t st,
-                              WaveWorkspace *ws, const builds::Choice &ch);
+                              WaveWorkspace *ws, const builds::Choice &ch, const uint32_t *tiles);
 
-hipError_t launch_render(const DeviceScene &s, const FrameParams &P, double *out, hipStream_t st, WaveWorkspace &ws) {
+hipError_t launch_render(const DeviceScene &s, const FrameParams &P, double *out, hipStream_t st, WaveWorkspace &ws,
+                         const uint32_t *tiles) {
     ws.ran = builds::Ran{};  // what this call launches: set below and in launch_render_wave, where a launch is made
     if (P.tile_count == 0) return hipSuccess;
     ws.refusal[0] = 0;
@@ -263,14 +264,16 @@ hipError_t launch_render(const DeviceScene &s, const FrameParams &P, double *out
     in.scene_diag = s.view.diag;
     in.depth = P.depth;
     in.samples = (uint64_t)P.tile_count * TILE * TILE * P.spp;
-    in.window = P.s_begin > 0 || (P.s_end && P.s_end < P.spp);
+    // (a listed launch is treated like a sample window: only the wavefront engine knows the tile map)
+    in.window = P.s_begin > 0 || (P.s_end && P.s_end < P.spp) || tiles != nullptr;
     in.window_empty = P.s_begin >= (P.s_end ? P.s_end : P.spp);
     in.wave_diag_on = PT_WAVE_DIAG && ws.diag;
     in.diag_buffer = ws.diag != nullptr;
     in.tune = ws.tune;
     const builds::Choice ch = builds::choose(in);
     if (ch.engine == builds::REFUSE) return hipErrorInvalidValue;
-    if (ch.engine == builds::WAVE) return launch_render_wave(s.view, P, out, st, &ws, ch);
+    if (ch.engine == builds::WAVE) return launch_render_wave(s.view, P, out, st, &ws, ch, tiles);
+    if (tiles) return hipErrorInvalidValue;  // (never: a listed launch is a window)
     hipError_t e0 = timer_begin(ws.timer, st, K_MEGA);
     if (e0 != hipSuccess) return e0;
     bool launched = false;

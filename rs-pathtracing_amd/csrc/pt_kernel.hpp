@@ -68,7 +68,11 @@ void wave_workspace_free(WaveWorkspace *ws);
 
 // Renders this rank's tiles of P into out with the engine and the kernel builds that builds::choose picks
 // (pt_builds.hpp).  An error with ws.refusal set is a refusal, not a HIP failure.
-hipError_t launch_render(const DeviceScene &s, const FrameParams &P, double *out, hipStream_t st, WaveWorkspace &ws);
+// tiles (a host array of P.tile_count entries that passes tile_list_ok, with P.tile_begin 0; null: none): a listed
+// launch, which renders entries tiles[0..tile_count) of the rank's tile list and touches no other tile (DESIGN.md
+// §3.11).  It always runs the wavefront engine; the list is copied before the call returns.
+hipError_t launch_render(const DeviceScene &s, const FrameParams &P, double *out, hipStream_t st, WaveWorkspace &ws,
+                         const uint32_t *tiles = nullptr);
 // rows [y0, y1) of the frame from gathered shards (pt_unshard_device)
 hipError_t launch_unshard(const double *gathered, uint32_t width, uint32_t height, uint32_t world, double *frame,
                           hipStream_t st, uint32_t y0 = 0, uint32_t y1 = ~0u);

@@ -43,6 +43,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "pt_lprof.hpp"  // tuning instrumentation (compiled out of the product builds)
@@ -126,6 +127,9 @@ struct WfView {
     uint32_t npix;  // pixels of the tile group (tiles * 256)
     uint32_t s0, ns;  // sample range of the chunk
     uint32_t tile0;   // first tile of the group (index in this rank's tile list)
+    // a listed launch (launch_render's `tiles`): position tile0 + g of the launch stands for entry
+    // tile_map[tile0 + g] of the rank's tile list; null: the position is the entry
+    const uint32_t *tile_map;
 };
 
 // What a launch of the wavefront kernels reads besides its iteration: the
@@ -139,7 +143,8 @@ struct WfView {
 // its use rather than a value held in an SGPR for the whole kernel (by value,
 // the loop-invariant arguments and their derived addresses spilled 60-70
 // SGPRs of the bounce builds to VGPR lanes, round 5).
-struct WfArgs {
+// (64-byte aligned: every block of a frame's array starts a cache line, whatever the view's size)
+struct alignas(64) WfArgs {
     dev::Scene sc;
     FrameParams P;
     WfView v;
@@ -258,19 +263,29 @@ __device__ __forceinline__ uint32_t *deep_count(const WfView &v, uint32_t depth,
 }
 
 // Pixel of a path slot: slot = (s_local * tiles + ti_local) * 256 + thread-in-tile,
-// thread-in-tile laid out as render_tiles' 4 waves of 8x8.
-__device__ __forceinline__ void slot_pixel(const FrameParams &P, const WfView &v, uint32_t id, uint32_t *x,
-                                           uint32_t *y, uint32_t *s_local, uint32_t *pix_local) {
+// thread-in-tile laid out as render_tiles' 4 waves of 8x8.  Returns the tile's index in the rank's tile list.
+// A listed launch (WfView::tile_map) looks the index up at the slot's position.  Every caller's 256-thread block
+// works on one tile (block bases and npix are multiples of 256), so the position is the same in every lane of a
+// wave: the entry is one scalar load per wave, not a load per lane and sample.
+__device__ __forceinline__ uint32_t slot_pixel(const FrameParams &P, const WfView &v, uint32_t id, uint32_t *x,
+                                               uint32_t *y, uint32_t *s_local, uint32_t *pix_local) {
     const uint32_t within = id % v.npix;
     *s_local = id / v.npix;
     *pix_local = within;
-    const uint32_t ti = v.tile0 + within / (TILE * TILE);
+    uint32_t ti = v.tile0 + within / (TILE * TILE);
+    if (const uint32_t *map = v.tile_map) {
+        // (the list is written before the frame's first launch and never during it: constant address space, as
+        // kargs reads the argument blocks)
+        typedef const __attribute__((address_space(4))) uint32_t *cmap;
+        ti = ((cmap)map)[__builtin_amdgcn_readfirstlane(ti)];
+    }
     const uint32_t th = within % (TILE * TILE);
     const uint32_t k = dev::tile_position(P.rank + ti * P.world, P.tiles_x, P.world);
     const uint32_t tx = k % P.tiles_x, ty = k / P.tiles_x;
     const uint32_t w = th >> 6, l = th & 63;
     *x = tx * TILE + (((w & 1u) << 3) | (l & 7u));
     *y = ty * TILE + (((w >> 1) << 3) | (l >> 3));
+    return ti;
 }
 
 // points along a march job's chord whose sign of f predicts a hit (queue
@@ -1037,8 +1052,7 @@ __global__ __launch_bounds__(256) void wf_reduce(const WfArgs *__restrict__ A, i
     }
     if (pl >= v.npix) return;
     uint32_t x, y, sl, pl2;
-    slot_pixel(P, v, pl, &x, &y, &sl, &pl2);
-    const uint32_t ti = v.tile0 + pl / (TILE * TILE), th = pl % (TILE * TILE);
+    const uint32_t ti = slot_pixel(P, v, pl, &x, &y, &sl, &pl2), th = pl % (TILE * TILE);
     const uint32_t w = th >> 6, l = th & 63;
     const uint32_t lx = ((w & 1u) << 3) | (l & 7u), ly = ((w >> 1) << 3) | (l >> 3);
     double *dst = P.compact ? out + ((size_t)ti * (TILE * TILE) + ly * TILE + lx) * 3
@@ -1346,9 +1360,10 @@ static hipStream_t slot_stream(const WaveWorkspace *ws, hipStream_t st, int j) {
 
 // Queues this rank's tiles of the frame (of a resumable frame: the window [s_begin, s_end) of its samples) on st:
 // the plan (pt_plan.hpp), the workspace, the chunks' argument blocks, then the chunks step by step, with the kernel
-// builds of `bc` (builds::choose, pt_builds.hpp).
+// builds of `bc` (builds::choose, pt_builds.hpp).  tiles (host, P0.tile_count entries, P0.tile_begin 0; null: none):
+// a listed launch, whose position g is entry tiles[g] of the rank's list (WfView::tile_map); copied before returning.
 hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, double *out, hipStream_t st,
-                              WaveWorkspace *ws, const builds::Choice &bc) {
+                              WaveWorkspace *ws, const builds::Choice &bc, const uint32_t *tiles) {
     if (P0.tile_count == 0 || P0.spp == 0) return hipSuccess;
     const Tuning &tu = ws->tune;
     plan::Input in;
@@ -1428,14 +1443,24 @@ hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
     // The launches' argument blocks (WfArgs): chunk ci at iteration parity h is block 2 ci + h.  They are
     // written to the pinned staging buffer, which the previous frame's copy must have read, and copied to the
     // device on st after the previous frame's kernels (the wait on ws->done above), before the side streams fork.
+    // A listed launch's tile list rides behind the blocks in the same staging buffer and the same copy, so the
+    // blocks' lifetime rules are the list's: it is not overwritten while a queued frame reads it.
     const size_t nargs = chunk_list.size() * 2;
-    if ((e = reserve_args(ws, nargs * sizeof(WfArgs))) != hipSuccess) return e;
+    const size_t list_off = (nargs * sizeof(WfArgs) + 15) & ~(size_t)15;
+    const size_t args_bytes = tiles ? list_off + (size_t)P0.tile_count * sizeof(uint32_t) : nargs * sizeof(WfArgs);
+    if ((e = reserve_args(ws, args_bytes)) != hipSuccess) return e;
     WfArgs *ah = (WfArgs *)ws->args_host, *ad = (WfArgs *)ws->args_dev;
+    const uint32_t *tile_map = nullptr;
+    if (tiles) {
+        memcpy((char *)ws->args_host + list_off, tiles, (size_t)P0.tile_count * sizeof(uint32_t));
+        tile_map = (const uint32_t *)((char *)ws->args_dev + list_off);
+    }
     for (size_t ci = 0; ci < chunk_list.size(); ci++) {
         const plan::Chunk &ch = chunk_list[ci];
         const int j = ch.slot;
         WfView v = sl[j].v;
         v.tile0 = P0.tile_begin + ch.g0;
+        v.tile_map = tile_map;
         v.npix = ch.gt * TILE * TILE;
         v.s0 = ch.s0;
         v.ns = ch.ns;
@@ -1445,7 +1470,7 @@ hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
             ah[2 * ci + h] = WfArgs{sc, P0, v};
         }
     }
-    if ((e = hipMemcpyAsync(ad, ah, nargs * sizeof(WfArgs), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(ad, ah, args_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
     if ((e = hipEventRecord(ws->args_ev, st)) != hipSuccess) return e;
     ws->args_pending = true;
     // the side streams start after everything the caller queued on st

@@ -11,6 +11,15 @@ under the per-kind kernel timing (pt_kernel_timing), to show where the time goes
 
     python scripts/adaptive_bench.py [--rounds 5] [--width 1920 --height 1080 --cap 256 --window 32]
 
+List mode (profiles/r14/adaptive_list.txt): "list" among --gaps is the frame whose windows are one
+launch each over the list of the still-active tiles (pt_render_adaptive_list_device), and --list is short for --gaps
+list,1024: the listed frame beside the run-based frame at the default merge_gap and the uniform frame, in the same
+alternating rounds.  The result then has a "list" table: per threshold the samples kept, the listed frame's time, its
+ratio to the uniform frame, the time a perfect conversion of samples into time would give (kept x uniform) and what
+is left over, and the listed frame's launches and kernel time by kind.
+
+    python scripts/adaptive_bench.py --list
+
 Needs a GPU (there is no fallback)."""
 import argparse
 import json
@@ -22,6 +31,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
 JOIN_ALL = 0xFFFFFFFF
+LIST = -1  # not a merge_gap: the listed frame
 
 
 def main():
@@ -36,7 +46,10 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--thresholds", default="0.05,0.1,0.2")
     ap.add_argument("--gaps", default="0,4,16,64,256,1024,all")
+    ap.add_argument("--list", action="store_true", help="the listed frame beside merge_gap 1024: --gaps list,1024")
     args = ap.parse_args()
+    if args.list:
+        args.gaps = "list,1024"
 
     import numpy as np
     import torch
@@ -48,7 +61,7 @@ def main():
     w, h, cap, window = args.width, args.height, args.cap, args.window
     windows = (cap + window - 1) // window
     thresholds = [float(t) for t in args.thresholds.split(",")]
-    gaps = [JOIN_ALL if g == "all" else int(g) for g in args.gaps.split(",")]
+    gaps = [JOIN_ALL if g == "all" else LIST if g == "list" else int(g) for g in args.gaps.split(",")]
     scene = pt.Scene.from_json((ROOT / "scenes" / args.scene).read_text(), seed=1)
     r = pt.HipRenderer(scene, device=0, depth=args.depth)
     cam = scene.camera()
@@ -75,7 +88,8 @@ def main():
         def fn():
             launched[(threshold, gap)] = r.render_adaptive_device(
                 cam, w, h, cap, threshold, args.seed, 0, 1, frame.data_ptr(), var.data_ptr(), ts.data_ptr(),
-                te.data_ptr(), work.data_ptr(), st, window=window, merge_gap=gap)
+                te.data_ptr(), work.data_ptr(), st, window=window,
+                **(dict(tile_list=True) if gap == LIST else dict(merge_gap=gap)))
         return fn
 
     def timed(fn):
@@ -87,7 +101,7 @@ def main():
         return a.elapsed_time(b)
 
     def gap_name(g):
-        return "all" if g == JOIN_ALL else str(g)
+        return "all" if g == JOIN_ALL else "list" if g == LIST else str(g)
 
     legs = [("uniform_%dspp_%dw" % (cap, windows), uniform_frame)]
     legs += [("thr%g_gap%s" % (t, gap_name(g)), adaptive(t, g)) for t in thresholds for g in gaps]
@@ -113,13 +127,13 @@ def main():
 
     kinds = {}
     for t in thresholds:
-        for g in (0, 16):
+        for g in (LIST, 0, 16):
             if g not in gaps:
                 continue
             pt.kernel_timing(r, True)
             total = timed(adaptive(t, g))
             k = pt.kernel_timing(r, False)
-            kinds["thr%g_gap%d" % (t, g)] = {"frame_ms": round(total, 3),
+            kinds["thr%g_gap%s" % (t, gap_name(g))] = {"frame_ms": round(total, 3),
                                              "kernel_ms": {a: round(v[0], 3) for a, v in k.items() if v[1]},
                                              "launches": {a: v[1] for a, v in k.items() if v[1]}}
     pt.kernel_timing(r, True)
@@ -143,6 +157,22 @@ def main():
                           "samples_kept_over_full": round(kept / full, 4),
                           "samples_launched_over_full": round(launched[(t, g)] / full, 4)})
         table.append({"threshold": t, "tiles_by_samples": hist})
+    listed = []
+    if LIST in gaps:
+        spread = max(ms[legs[0][0]]) - min(ms[legs[0][0]])
+        for t in thresholds:
+            name = "thr%g_gaplist" % t
+            kept = int(np.sum(pixels * tiles[t])) / full
+            spread_t = max(spread, max(ms[name]) - min(ms[name]))
+            listed.append({"threshold": t, "samples_kept_over_full": round(kept, 4),
+                           "samples_launched_over_full": round(launched[(t, LIST)] / full, 4),
+                           "list_median_ms": round(med[name], 3),
+                           "list_min_max_ms": [round(min(ms[name]), 3), round(max(ms[name]), 3)],
+                           "time_over_uniform": round(med[name] / base, 4),
+                           "perfect_conversion_ms": round(kept * base, 3),
+                           "left_over_ms": round(med[name] - kept * base, 3),
+                           "faster_than_uniform_by_more_than_the_spread": bool(base - med[name] > spread_t),
+                           "kernel_timing": kinds.get(name)})
     res = {
         "workload": "%s %dx%d depth %d, window %d, cap %d" % (args.scene, w, h, args.depth, window, cap),
         "version": pt.version(),
@@ -151,6 +181,7 @@ def main():
         "uniform_median_ms": round(base, 3),
         "uniform_min_max_ms": [round(min(ms[legs[0][0]]), 3), round(max(ms[legs[0][0]]), 3)],
         "table": table,
+        **({"list": listed} if listed else {}),
         "ms": {name: [round(x, 3) for x in v] for name, v in ms.items()},
         "kernel_timing": kinds,
         "cap_tiles_equal_uniform_frame": cap_tiles_equal_uniform,

@@ -31,8 +31,9 @@
 //     the cap; inf: stop every tile at the second window), judged after each window of -B samples (default 8;
 //     min_samples 0, luminance floor 0.01, the library's recommended merge_gap).  -M: the samples each tile stopped
 //     at, as uint32, tiles row-major.  With -A, -V writes the adaptive frame's variance plane (each pixel's at its
-//     tile's own sample count) and -D uses it.  -A with -c or -W, and -B or -M without -A, are usage errors: the
-//     accumulation state is not checkpointed.
+//     tile's own sample count) and -D uses it.  -L: every window is one launch over the list of the still-active
+//     tiles (pt_render_adaptive_list): the same files, bit for bit, and no stopped tile rendered again.
+//     -A with -c or -W, and -B, -M or -L without -A, are usage errors: the accumulation state is not checkpointed.
 // Exit status: 0 done, 1 error (the library's message on stderr), 2 usage, 3 stopped with a checkpoint.
 #include <hip/hip_runtime_api.h>
 
@@ -55,7 +56,8 @@ int usage() {
                  "usage: pt_render scene.json [spp [w h]] [-d depth] [-s seed] [-o image.png|.ppm] [-f frame.f64]\n"
                  "                 [-c checkpoint -n window_spp [-x windows]] [-a aov_prefix] [-D denoised.png]\n"
                  "                 [-V variance.f64 [-W windows]]   (-V cannot be combined with -c)\n"
-                 "                 [-A threshold [-B window] [-M tiles.u32]]   (spp is the cap; not with -c or -W)\n");
+                 "                 [-A threshold [-B window] [-M tiles.u32] [-L]]   (spp is the cap; not with -c or -W;\n"
+                 "                                                                   -L: one launch per window)\n");
     return 2;
 }
 
@@ -102,7 +104,7 @@ int main(int argc, char **argv) {
     uint32_t depth = 50, window = 0, stop_after = 0, var_windows = 0, ad_window = 0;
     uint64_t seed = 1;
     double ad_threshold = 0.0;
-    bool adaptive = false, ad_window_given = false;
+    bool adaptive = false, ad_window_given = false, ad_list = false;
     std::string out_img = "rendered.png", out_f64, ckpt, aov, denoised, out_var, out_tiles;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -133,6 +135,7 @@ int main(int argc, char **argv) {
             ad_window = (uint32_t)std::strtoul(val("-B"), nullptr, 10);
             ad_window_given = true;
         } else if (a == "-M") out_tiles = val("-M");
+        else if (a == "-L") ad_list = true;
         else if (a == "-x") stop_after = (uint32_t)std::strtoul(val("-x"), nullptr, 10);
         else if (a.size() > 1 && a[0] == '-') return usage();
         else pos.push_back(argv[i]);
@@ -140,7 +143,7 @@ int main(int argc, char **argv) {
     if (pos.empty() || pos.size() == 3 || pos.size() > 4 || (!ckpt.empty() && window == 0)) return usage();
     if (!out_var.empty() && !ckpt.empty()) return usage();
     if (adaptive && (!ckpt.empty() || var_windows != 0)) return usage();
-    if (!adaptive && (ad_window_given || !out_tiles.empty())) return usage();
+    if (!adaptive && (ad_window_given || !out_tiles.empty() || ad_list)) return usage();
     const uint32_t spp = pos.size() >= 2 ? (uint32_t)std::strtoul(pos[1], nullptr, 10) : 100;  // the GUI's 100
     const uint32_t w = pos.size() == 4 ? (uint32_t)std::strtoul(pos[2], nullptr, 10) : 1600;    // main.rs:26
     const uint32_t h = pos.size() == 4 ? (uint32_t)std::strtoul(pos[3], nullptr, 10) : 900;
@@ -166,10 +169,13 @@ int main(int argc, char **argv) {
         uint64_t launched = 0;
         variance.resize(npix * 3);
         if (!ad_window_given) ad_window = PT_ADAPTIVE_WINDOW;
-        if ((rc = pt_render_adaptive(r, &cam, w, h, ad_window, 0, spp, ad_threshold, PT_ADAPTIVE_LUMINANCE_FLOOR,
-                                     PT_ADAPTIVE_MERGE_GAP, seed, rgb.data(), variance.data(), tile_samples.data(),
-                                     nullptr, &launched)))
-            return fail("adaptive render", rc);
+        rc = ad_list ? pt_render_adaptive_list(r, &cam, w, h, ad_window, 0, spp, ad_threshold,
+                                               PT_ADAPTIVE_LUMINANCE_FLOOR, seed, rgb.data(), variance.data(),
+                                               tile_samples.data(), nullptr, &launched)
+                     : pt_render_adaptive(r, &cam, w, h, ad_window, 0, spp, ad_threshold, PT_ADAPTIVE_LUMINANCE_FLOOR,
+                                          PT_ADAPTIVE_MERGE_GAP, seed, rgb.data(), variance.data(),
+                                          tile_samples.data(), nullptr, &launched);
+        if (rc) return fail("adaptive render", rc);
         std::fprintf(stderr, "pt_render: %llu of %llu pixel-samples rendered\n", (unsigned long long)launched,
                      (unsigned long long)npix * spp);
         if (!out_var.empty() && !write_doubles(out_var, variance)) return 1;
