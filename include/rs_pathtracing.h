@@ -322,6 +322,61 @@ int pt_denoise(int device, const double *rgb, const double *albedo, const double
                uint32_t width, uint32_t height, uint32_t iterations, double sigma_normal, double sigma_depth,
                double sigma_colour, uint32_t flags, double *out);
 
+/* ---- temporal accumulation: the last frame reprojected into a moved camera ---- */
+/* For a caller whose camera moves a little from frame to frame (an orbiting
+ * viewer at 1 spp): instead of starting every frame from nothing, the
+ * accumulated frame of the previous camera is reprojected into the new one
+ * through the new frame's first-hit distance, rejected where the geometry
+ * disagrees, and the new frame is blended in, so the denoiser that follows
+ * sees the samples of many frames.  All frames are in the colour buffer's
+ * layout (world == 1: width*height*3 doubles each, all finite): the colour,
+ * and the normal and depth planes of pt_render_aov for the same camera (of
+ * depth, [0] and [1] are read: their quotient is the mean hit distance).
+ * The history is pt_temporal_history_doubles(width, height) = width*height*8
+ * doubles, 16-byte aligned: two 32-byte records per pixel p = x + y*width,
+ * first all colour records, then all guide records:
+ *   colour record {h0, h1, h2, n}: the accumulated colour and the number of
+ *     frames it stands for (a double, at least 1 once written);
+ *   guide record {m0, m1, m2, z}: the normal plane's value and the hit
+ *     distance of the frame that wrote it; z = 0 for a pixel with no hit.
+ * A call reads history_in (written by the call for prev_camera) and writes
+ * history_out; a caller keeps two and swaps them.  history_in == NULL together
+ * with prev_camera == NULL is the first frame: every pixel starts at n = 1.
+ * Per pixel: the point the centre ray hits at the mean hit distance is
+ * projected into prev_camera; the four history pixels around it are weighted
+ * bilinearly (a position within 1/1024 of a pixel centre takes that pixel
+ * alone, so a still camera accumulates without blur); a tap counts only if
+ * its normal lies within sigma_normal of the new one and its hit distance
+ * within sigma_depth, relative, of the point's distance to prev_camera; the
+ * new colour is blended in with weight 1/n, n = the taps' count + 1 capped at
+ * max_count.  A pixel with no hit, a point behind or outside prev_camera's
+ * frame, or no counting tap starts again at n = 1.  f64, no transcendental
+ * function, one fixed order: the same bits on every run, equal to the numpy
+ * restatement in tests/temporalref.py.  Step by step:
+ * rs-pathtracing_amd/csrc/pt_temporal.hpp and DESIGN.md 3.12.
+ * Defaults: max_count 32, sigma_normal 0.5, sigma_depth 0.1; +inf is a legal
+ * sigma and means that test always passes.  d_out (the accumulated frame,
+ * equal to the colour records) may be d_rgb; history_in and history_out must
+ * not overlap.  PT_ERR_INVALID, the call writing nothing: a NULL required
+ * pointer, a zero size, max_count 0, a sigma not greater than 0 or NaN,
+ * exactly one of prev_camera and history_in NULL, a device history pointer
+ * that is not 16-byte aligned, history_in overlapping history_out, a frame of
+ * more than 2^31 - 1 tiles of 16x16.  Objects that move, sky pixels and
+ * sharded frames (accumulate after pt_unshard_device) are not handled.
+ * (Library 0.4.3; no ABI change.) */
+/* doubles of one history buffer for a width x height frame (0 if either is 0) */
+size_t pt_temporal_history_doubles(uint32_t width, uint32_t height);
+/* queued on hip_stream of HIP device `device` (-1 = current), like pt_denoise_device; needs no renderer */
+int pt_temporal_device(int device, const double *d_rgb, const double *d_normal, const double *d_depth,
+                       const pt_camera *camera, const pt_camera *prev_camera, uint32_t width, uint32_t height,
+                       const double *d_history_in, double *d_history_out, uint32_t max_count,
+                       double sigma_normal, double sigma_depth, double *d_out, void *hip_stream);
+/* the same from and to host buffers (the histories too); allocates, copies, blocks */
+int pt_temporal(int device, const double *rgb, const double *normal, const double *depth,
+                const pt_camera *camera, const pt_camera *prev_camera, uint32_t width, uint32_t height,
+                const double *history_in, double *history_out, uint32_t max_count,
+                double sigma_normal, double sigma_depth, double *out);
+
 /* ---- per-pixel variance from sample windows, and the denoiser's variance term ---- */
 /* How far a frame is from converged, per pixel and channel: the variance of the
  * pixel's mean (its square root is the standard error), estimated by batch

@@ -52,6 +52,7 @@ EXPORTS = [
     "pt_render_device_samples", "pt_checkpoint_save", "pt_checkpoint_load",
     "pt_render_aov_device", "pt_render_aov",
     "pt_denoise_workspace_doubles", "pt_denoise_device", "pt_denoise",
+    "pt_temporal_history_doubles", "pt_temporal_device", "pt_temporal",
     "pt_variance_workspace_doubles", "pt_variance_window_device", "pt_render_variance_device", "pt_render_variance",
     "pt_denoise_variance_device", "pt_denoise_variance",
     "pt_adaptive_workspace_doubles", "pt_render_adaptive_device", "pt_render_adaptive",
@@ -62,6 +63,9 @@ ADAPTIVE_FLOOR = 0.01
 ADAPTIVE_MERGE_GAP = 1024
 DENOISE_DEMODULATE = 1  # PT_DENOISE_DEMODULATE
 DENOISE_MAX_ITERATIONS = 8  # PT_DENOISE_MAX_ITERATIONS
+TEMPORAL_MAX_COUNT = 32  # the recommended defaults of pt_temporal_device (rs_pathtracing.h)
+TEMPORAL_SIGMA_NORMAL = 0.5
+TEMPORAL_SIGMA_DEPTH = 0.1
 ABI_VERSION = 4  # PT_ABI_VERSION this binding is written for
 
 
@@ -171,6 +175,11 @@ def lib():
         "pt_denoise_device": (C.c_int, [C.c_int, vp, vp, vp, vp, u32, u32, u32, C.c_double, C.c_double, C.c_double,
                                         u32, vp, vp, vp]),
         "pt_denoise": (C.c_int, [C.c_int, d, d, d, d, u32, u32, u32, C.c_double, C.c_double, C.c_double, u32, d]),
+        "pt_temporal_history_doubles": (sz, [u32, u32]),
+        "pt_temporal_device": (C.c_int, [C.c_int, vp, vp, vp, C.POINTER(CameraStruct), C.POINTER(CameraStruct), u32, u32,
+                                         vp, vp, u32, C.c_double, C.c_double, vp, vp]),
+        "pt_temporal": (C.c_int, [C.c_int, d, d, d, C.POINTER(CameraStruct), C.POINTER(CameraStruct), u32, u32, d, d, u32,
+                                  C.c_double, C.c_double, d]),
         "pt_variance_workspace_doubles": (sz, [u32, u32, u32, u32]),
         "pt_variance_window_device": (C.c_int, [C.c_int, vp, sz, u32, u32, u32, u32, vp, vp, vp]),
         "pt_render_variance_device": (C.c_int, [vp, C.POINTER(CameraStruct), u32, u32, u32, u64, u32, u32, u32, vp, vp,
@@ -808,6 +817,57 @@ def denoise(rgb: np.ndarray, albedo, normal: np.ndarray, depth: np.ndarray, widt
                             int(iterations), float(sigma_normal), float(sigma_depth), float(sigma_colour),
                             DENOISE_DEMODULATE if demodulate else 0, _dptr(out)))
     return out
+
+
+def temporal_history_doubles(width: int, height: int) -> int:
+    """Doubles of one history buffer of temporal_device for a width x height frame (pt_temporal_history_doubles):
+    width*height*8, first all colour records {h0, h1, h2, n}, then all guide records {m0, m1, m2, z}."""
+    return int(lib().pt_temporal_history_doubles(int(width), int(height)))
+
+
+def temporal_device(rgb_ptr: int, normal_ptr: int, depth_ptr: int, camera: "Camera", prev_camera, width: int,
+                    height: int, history_in_ptr: int, history_out_ptr: int, out_ptr: int,
+                    max_count: int = TEMPORAL_MAX_COUNT, sigma_normal: float = TEMPORAL_SIGMA_NORMAL,
+                    sigma_depth: float = TEMPORAL_SIGMA_DEPTH, stream_ptr: int = 0, device: int = -1):
+    """Temporal accumulation on frames in device memory (pt_temporal_device): the colour of `camera`'s frame and its
+    normal and depth planes (width*height*3 doubles each), blended with the history at history_in_ptr, which the
+    call for prev_camera wrote, into out_ptr (which may be rgb_ptr) and the history at history_out_ptr
+    (temporal_history_doubles(width, height) doubles each, 16-byte aligned, not overlapping), queued on stream_ptr.
+    prev_camera None with history_in_ptr 0 is the first frame."""
+    _check(lib().pt_temporal_device(int(device), C.c_void_p(rgb_ptr or None), C.c_void_p(normal_ptr or None),
+                                    C.c_void_p(depth_ptr or None), None if camera is None else C.byref(camera._c),
+                                    None if prev_camera is None else C.byref(prev_camera._c), int(width), int(height),
+                                    C.c_void_p(history_in_ptr or None), C.c_void_p(history_out_ptr or None),
+                                    int(max_count), float(sigma_normal), float(sigma_depth),
+                                    C.c_void_p(out_ptr or None), C.c_void_p(stream_ptr)))
+
+
+def temporal(rgb: np.ndarray, normal: np.ndarray, depth: np.ndarray, camera: "Camera", prev_camera, width: int,
+             height: int, history_in=None, max_count: int = TEMPORAL_MAX_COUNT,
+             sigma_normal: float = TEMPORAL_SIGMA_NORMAL, sigma_depth: float = TEMPORAL_SIGMA_DEPTH,
+             device: int = -1):
+    """Temporal accumulation on host arrays (pt_temporal): a frame and the normal and depth planes render_aov gives
+    for it, (w*h, 3) float64 each, and the history the call for prev_camera returned (None with prev_camera None:
+    the first frame); returns the (w*h, 3) accumulated frame and the new history (w*h*8 doubles)."""
+    n = int(width) * int(height)
+    arrs = []
+    for a in (rgb, normal, depth):
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3)
+        if len(a) != n:
+            raise ValueError("each frame must hold width*height*3 doubles")
+        arrs.append(a)
+    hin = None
+    if history_in is not None:
+        hin = np.ascontiguousarray(history_in, dtype=np.float64).reshape(-1)
+        if len(hin) != n * 8:
+            raise ValueError("the history must hold width*height*8 doubles")
+    out = np.zeros((n, 3), dtype=np.float64)
+    hout = np.zeros(n * 8, dtype=np.float64)
+    _check(lib().pt_temporal(int(device), *[_dptr(a) for a in arrs], None if camera is None else C.byref(camera._c),
+                             None if prev_camera is None else C.byref(prev_camera._c), int(width), int(height),
+                             None if hin is None else _dptr(hin), _dptr(hout), int(max_count), float(sigma_normal),
+                             float(sigma_depth), _dptr(out)))
+    return out, hout
 
 
 def variance_workspace_doubles(width: int, height: int, rank: int = 0, world: int = 1) -> int:

@@ -26,6 +26,7 @@
 #include "pt_kernel.hpp"
 #include "pt_plan.hpp"
 #include "pt_scene.hpp"
+#include "pt_temporal.hpp"
 #include "pt_variance.hpp"
 
 using namespace pt;
@@ -1096,6 +1097,97 @@ int pt_denoise(int device, const double *rgb, const double *albedo, const double
         return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     HIP_TRY(hipMemcpy(out, dev[0].p, count * sizeof(double), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// ---- temporal accumulation (pt_temporal.hpp): the last frame reprojected into a moved camera, needs no renderer ----
+namespace {
+// the checks the device form and the host form share (the pointers are device or host memory alike)
+int temporal_args_refused(const double *rgb, const double *normal, const double *depth, const pt_camera *camera,
+                          const pt_camera *prev_camera, uint32_t w, uint32_t h, const double *history_in,
+                          const double *history_out, uint32_t max_count, double sigma_normal, double sigma_depth,
+                          const double *out) {
+    if (!rgb || !normal || !depth || !camera || !history_out || !out) return fail(PT_ERR_INVALID, "null argument");
+    if (w == 0 || h == 0) return fail(PT_ERR_INVALID, "width and height must be > 0");
+    if (max_count == 0) return fail(PT_ERR_INVALID, "max_count must be > 0");
+    if (!(sigma_normal > 0.0) || !(sigma_depth > 0.0))
+        return fail(PT_ERR_INVALID, "sigma_normal and sigma_depth must be > 0");
+    if ((prev_camera == nullptr) != (history_in == nullptr))
+        return fail(PT_ERR_INVALID, "prev_camera and history_in are given together, or neither (the first frame)");
+    const size_t doubles = temporal_history_doubles(w, h);
+    if (doubles == 0 || (uint64_t)tiles_x_of(w) * tiles_y_of(h) > 0x7fffffffull)
+        return fail(PT_ERR_INVALID, "the frame is too large to accumulate in one call");
+    if (history_in) {
+        const uintptr_t a = (uintptr_t)history_in, b = (uintptr_t)history_out, bytes = doubles * sizeof(double);
+        if (a < b + bytes && b < a + bytes) return fail(PT_ERR_INVALID, "history_in and history_out overlap");
+    }
+    return PT_OK;
+}
+
+dev::TemporalCam temporal_cam(const pt_camera &c, uint32_t w, uint32_t h) {
+    FrameParams fp;
+    caster_params(c, w, h, &fp);  // the very values the render uses
+    dev::TemporalCam t;
+    for (int k = 0; k < 3; k++) {
+        t.pos[k] = fp.pos[k];
+        t.right[k] = fp.right[k];
+        t.up[k] = fp.up[k];
+        t.lt[k] = fp.left_top[k];
+    }
+    t.res = fp.pixel_resolution;
+    return t;
+}
+}  // namespace
+
+size_t pt_temporal_history_doubles(uint32_t w, uint32_t h) { return temporal_history_doubles(w, h); }
+
+int pt_temporal_device(int device, const double *d_rgb, const double *d_normal, const double *d_depth,
+                       const pt_camera *camera, const pt_camera *prev_camera, uint32_t w, uint32_t h,
+                       const double *d_history_in, double *d_history_out, uint32_t max_count, double sigma_normal,
+                       double sigma_depth, double *d_out, void *stream) {
+    if (int rc = temporal_args_refused(d_rgb, d_normal, d_depth, camera, prev_camera, w, h, d_history_in,
+                                       d_history_out, max_count, sigma_normal, sigma_depth, d_out))
+        return rc;
+    if ((((uintptr_t)d_history_in | (uintptr_t)d_history_out) & 15u) != 0)
+        return fail(PT_ERR_INVALID, "the histories must be 16-byte aligned");
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    const dev::TemporalCam now = temporal_cam(*camera, w, h);
+    dev::TemporalCam prev{};
+    if (prev_camera) prev = temporal_cam(*prev_camera, w, h);
+    HIP_TRY(launch_temporal(d_rgb, d_normal, d_depth, w, h,
+                            temporal_consts(now, prev_camera ? &prev : nullptr,
+                                            prev_camera ? prev_camera->direction : nullptr,
+                                            prev_camera ? prev_camera->focal_length : 0.0, max_count, sigma_normal,
+                                            sigma_depth),
+                            d_history_in, d_history_out, d_out, (hipStream_t)stream));
+    return PT_OK;
+}
+
+int pt_temporal(int device, const double *rgb, const double *normal, const double *depth, const pt_camera *camera,
+                const pt_camera *prev_camera, uint32_t w, uint32_t h, const double *history_in, double *history_out,
+                uint32_t max_count, double sigma_normal, double sigma_depth, double *out) {
+    if (int rc = temporal_args_refused(rgb, normal, depth, camera, prev_camera, w, h, history_in, history_out,
+                                       max_count, sigma_normal, sigma_depth, out))
+        return rc;
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    const size_t count = (size_t)w * h * 3, hist = temporal_history_doubles(w, h);
+    const double *host[3] = {rgb, normal, depth};
+    DevBuf<double> dev[3], hin, hout;  // staging, freed on return; the frame is written in place in dev[0]
+    for (int k = 0; k < 3; k++) {
+        HIP_TRY(dev[k].alloc(count));
+        HIP_TRY(hipMemcpy(dev[k].p, host[k], count * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (history_in) {
+        HIP_TRY(hin.alloc(hist));
+        HIP_TRY(hipMemcpy(hin.p, history_in, hist * sizeof(double), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hout.alloc(hist));
+    if (int rc = pt_temporal_device(-1, dev[0].p, dev[1].p, dev[2].p, camera, prev_camera, w, h, hin.p, hout.p,
+                                    max_count, sigma_normal, sigma_depth, dev[0].p, nullptr))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpy(out, dev[0].p, count * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(history_out, hout.p, hist * sizeof(double), hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
