@@ -7,8 +7,9 @@
 
 namespace pt {
 
-// One workgroup = one 16x16 tile of the rank's list, aov_tiles' tile placement; thread t owns the pixel of tile-local
-// index i = t = lx + 16 * ly, so wave w holds i in [64w, 64w + 64) and a row of the tile is one run of 384 bytes.
+// One workgroup = one 16x16 tile of the rank's list, placed by pt_tiles.hpp, but not its lane_pixel: thread t owns the
+// pixel of tile-local index i = t = lx + 16 * ly (the tree below runs on i), so wave w holds i in [64w, 64w + 64) and
+// a row of the tile is one run of 384 bytes.
 // A stopped tile's block returns at once: tile_samples[ti] is one word, the same for the whole block.  The two tile
 // sums run together: steps 1..32 of the tree are shuffles inside the wave (lane i takes lane i + d's value; only the
 // lanes that are multiples of 2d hold tree values afterwards, and only lane 0's is used), steps 64 and 128 are the

@@ -4,7 +4,7 @@
 // target, or reaches the cap, is divided out into the frame and never touched again.  The windows go through
 // launch_render into a sums plane -- over ranges of the tile list (adaptive_runs), or over the list of the active tiles
 // in one launch (adaptive_list) -- and this pass runs on that plane.  f64, one
-// fixed order of operations, no transcendental function, so the GPU, the host build (tests/native/adaptive.mk) and
+// fixed order of operations, no transcendental function, so the GPU, the host build (tests/native/Makefile) and
 // the numpy restatement (tests/adaptiveref.py) give the same bits.
 //
 // Window k = 1..K covers samples [e_{k-1}, e_k), e_k = min(k * window, max_samples), n_k = e_k - e_{k-1}; K >= 2.
@@ -64,29 +64,19 @@ struct AdaptiveConsts {
     uint32_t cap;       // e_k == max_samples
 };
 
-// Where a tile of a rank's list lies, and where its pixels are kept: aov_tiles' geometry.
-struct AdaptiveGeom {
-    uint32_t width, height, rank, world, tiles_x, compact;
-};
+// Where the tiles of a rank's list lie and how their pixels are kept: the tile geometry (pt_tiles.hpp) under this
+// pass's own type name, which the kernel's and the launch's symbols carry.
+struct AdaptiveGeom : TileGeom {};
 
-// Pixel i = lx + 16 * ly of tile ti of the rank's list: its element offset in d_out's layout; false outside the frame
-// (a compact shard still has the offset: its padding).
+// This pass's two views of it, in the tile-local index i = lx + 16 * ly that its threads and its tree run on: the
+// element offset of pixel i of tile ti in d_out's layout, false outside the frame (a compact shard still has the
+// offset: its padding); and the tile's pixels inside the frame.
 PT_HD bool adaptive_pixel_at(const AdaptiveGeom &g, uint32_t ti, uint32_t i, size_t *at) {
-    const uint32_t k = tile_position(g.rank + ti * g.world, g.tiles_x, g.world);  // global tile id
-    const uint32_t tx = k % g.tiles_x, ty = k / g.tiles_x;
-    const uint32_t lx = i & (TILE - 1), ly = i / TILE;
-    const uint32_t x = tx * TILE + lx, y = ty * TILE + ly;
-    *at = g.compact ? ((size_t)ti * (TILE * TILE) + i) * 3 : ((size_t)y * g.width + x) * 3;
-    return x < g.width && y < g.height;
+    const TilePixel p = tile_pixel(g, ti, i & (TILE - 1), i / TILE);
+    *at = p.at;
+    return p.inside;
 }
-
-// The tile's pixels inside the frame.
-PT_HD uint32_t adaptive_tile_pixels(const AdaptiveGeom &g, uint32_t ti) {
-    const uint32_t k = tile_position(g.rank + ti * g.world, g.tiles_x, g.world);
-    const uint32_t x0 = (k % g.tiles_x) * TILE, y0 = (k / g.tiles_x) * TILE;
-    const uint32_t nx = g.width - x0 < TILE ? g.width - x0 : TILE, ny = g.height - y0 < TILE ? g.height - y0 : TILE;
-    return nx * ny;
-}
+PT_HD uint32_t adaptive_tile_pixels(const AdaptiveGeom &g, uint32_t ti) { return tile_pixels_inside(g, ti); }
 
 // One element after one window's render: S is its running sum; prev and q are not read when FIRST.  Returns q.
 template <bool FIRST>

@@ -27,6 +27,7 @@
 #include "pt_plan.hpp"
 #include "pt_scene.hpp"
 #include "pt_temporal.hpp"
+#include "pt_tiles.hpp"
 #include "pt_variance.hpp"
 
 using namespace pt;
@@ -63,22 +64,55 @@ int reg_depth_refused(uint32_t depth, const char *call) {
                                         std::to_string(PT_MAX_DEPTH));
 }
 
-uint32_t tiles_x_of(uint32_t w) { return (w + TILE - 1) / TILE; }
-uint32_t tiles_y_of(uint32_t h) { return (h + TILE - 1) / TILE; }
 // the smallest band of a progressive frame, in samples (enough paths to fill the device)
 constexpr uint64_t BAND_MIN_SAMPLES = (uint64_t)1 << 24;
 
 }  // namespace
 
 namespace {
+// A device buffer for the length of a call: the host forms and the probes stage their arrays in these.
 template <class T>
 struct DevBuf {
     T *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
+    size_t n = 0;
+    ~DevBuf() { (void)hipFree(p); }
+    hipError_t alloc(size_t count) {
+        n = count;
+        return hipMalloc(&p, (n ? n : 1) * sizeof(T));
     }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, (n ? n : 1) * sizeof(T)); }
+    // alloc, and the host array copied in; an optional array that is not given (null) gets no buffer: p stays null
+    hipError_t upload(const T *host, size_t count) {
+        if (!host) return hipSuccess;
+        const hipError_t e = alloc(count);
+        return e != hipSuccess ? e : hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice);
+    }
+    // the buffer copied out to the host array it was staged for (none: nothing to copy)
+    hipError_t download(T *host) const {
+        return host ? hipMemcpy(host, p, n * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess;
+    }
 };
+
+// The refusals that recur: each message stands here once, and an entry point calls them in its own order.
+int refuse_if(bool bad, const char *msg) { return bad ? fail(PT_ERR_INVALID, msg) : PT_OK; }
+int frame_refused(uint32_t w, uint32_t h) { return refuse_if(w == 0 || h == 0, "width and height must be > 0"); }
+int frame_refused(uint32_t w, uint32_t h, uint32_t spp) {
+    return refuse_if(w == 0 || h == 0 || spp == 0, "width, height and samples_number must be > 0");
+}
+int rank_refused(uint32_t rank, uint32_t world) { return refuse_if(world == 0 || rank >= world, "rank must be < world"); }
+int sample_window_refused(uint32_t s_begin, uint32_t s_end, uint32_t spp) {
+    return refuse_if(s_begin >= s_end || s_end > spp,
+                     "sample window must satisfy 0 <= s_begin < s_end <= samples_number");
+}
+int windows_refused(uint32_t windows, uint32_t spp) {
+    return refuse_if(windows < 2 || windows > spp, "windows must be 2..samples_number");
+}
+int sigmas_refused(double sigma_normal, double sigma_depth) {
+    return refuse_if(!(sigma_normal > 0.0) || !(sigma_depth > 0.0), "sigma_normal and sigma_depth must be > 0");
+}
+int workspace_refused(const void *d_work) {
+    if (!d_work) return fail(PT_ERR_INVALID, "null argument");
+    return refuse_if(((uintptr_t)d_work & 15u) != 0, "the workspace must be 16-byte aligned");
+}
 }  // namespace
 
 struct pt_scene {
@@ -144,6 +178,11 @@ struct pt_renderer {
     int device() const { return gpus[0].device; }
     hipStream_t stream() const { return gpus[0].stream; }
 };
+
+static int in_flight_refused(const pt_renderer *r) {
+    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
+    return PT_OK;
+}
 
 extern "C" {
 
@@ -439,7 +478,19 @@ FrameParams frame_params(const pt_renderer *r, const pt_camera &cam, uint32_t w,
     FrameParams P = pt::frame_params(cam, w, h, spp, r->depth, seed, r->s11);
     P.rank = 0;
     P.world = 1;
-    P.tiles_x = tiles_x_of(w);
+    P.tiles_x = tiles_across(w);
+    return P;
+}
+
+// The FrameParams of one rank's whole shard (world > 1: in the compact layout).
+FrameParams shard_params(const pt_renderer *r, const pt_camera &cam, uint32_t w, uint32_t h, uint32_t spp,
+                         uint64_t seed, uint32_t rank, uint32_t world) {
+    FrameParams P = frame_params(r, cam, w, h, spp, seed);
+    P.rank = rank;
+    P.world = world;
+    P.compact = world > 1 ? 1 : 0;
+    P.tile_begin = 0;
+    P.tile_count = shard_tiles(w, h, rank, world);
     return P;
 }
 
@@ -479,7 +530,7 @@ int frame_prologue(pt_renderer *r, uint32_t w, uint32_t h) {
     const uint32_t world = (uint32_t)r->gpus.size();
     if (world == 1) return PT_OK;
     GpuShare &g0 = r->gpus[0];
-    const size_t per = pt_shard_tiles(w, h, 0, world);
+    const size_t per = shard_tiles(w, h, 0, world);
     HIP_TRY(hipSetDevice(g0.device));
     if (int rc = grow(&r->d_gather, &r->gather_cap, (size_t)world * per * TILE * TILE * 3)) return rc;
     HIP_TRY(hipEventRecord(g0.shard_ev, g0.stream));
@@ -501,7 +552,7 @@ int enqueue_band(pt_renderer *r, const FrameParams &P0, double *d_frame, uint8_t
     const uint32_t world = (uint32_t)r->gpus.size();
     const uint32_t w = P0.width, h = P0.height, tx = P0.tiles_x;
     GpuShare &g0 = r->gpus[0];
-    const size_t per = pt_shard_tiles(w, h, 0, world);
+    const size_t per = shard_tiles(w, h, 0, world);
     const uint32_t row0 = t0 * TILE, row1 = t1 * TILE < h ? t1 * TILE : h;
     for (uint32_t k = 0; k < world; k++) {
         GpuShare &g = r->gpus[k];
@@ -770,7 +821,7 @@ void pt_renderer_destroy(pt_renderer *r) {
 
 int pt_render_start(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed) {
     if (!r || !cam) return fail(PT_ERR_INVALID, "null argument");
-    if (w == 0 || h == 0 || spp == 0) return fail(PT_ERR_INVALID, "width, height and samples_number must be > 0");
+    if (int rc = frame_refused(w, h, spp)) return rc;
     if (r->started) {  // a new frame replaces the one in flight (the reference stops it first, main.rs:268)
         if (int rc = pt_render_stop(r)) return rc;
     }
@@ -784,8 +835,8 @@ int pt_render_start(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h
     // BAND_MIN_SAMPLES: a band of the reference GUI's 1-spp preview at 1600x900 (main.rs:264) would otherwise be
     // 160k samples, a chain of ~260 launches that each find a few paths (a 78 ms frame, round 5).  The stop
     // latency does not depend on the band size (stop_gate runs at every chunk start and compaction).
-    const uint32_t ty = tiles_y_of(h);
-    const uint64_t row_samples = (uint64_t)tiles_x_of(w) * TILE * TILE * spp;
+    const uint32_t ty = tiles_across(h);
+    const uint64_t row_samples = (uint64_t)tiles_across(w) * TILE * TILE * spp;
     const uint32_t min_rows = (uint32_t)((BAND_MIN_SAMPLES + row_samples - 1) / row_samples);
     uint32_t band = ty >= 8 ? ty / 8 : 1;
     if (band < min_rows) band = min_rows < ty ? min_rows : ty;
@@ -891,9 +942,7 @@ int pt_render_stop(pt_renderer *r) {
 }
 
 uint32_t pt_shard_tiles(uint32_t w, uint32_t h, uint32_t rank, uint32_t world) {
-    if (world == 0 || rank >= world) return 0;
-    uint32_t total = tiles_x_of(w) * tiles_y_of(h);
-    return rank < total ? (total - rank + world - 1) / world : 0;
+    return shard_tiles(w, h, rank, world);
 }
 
 int pt_render_device(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
@@ -901,61 +950,48 @@ int pt_render_device(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t 
     return pt_render_device_samples(r, cam, w, h, spp, seed, rank, world, 0, spp, d_out, stream);
 }
 
-int pt_render_device_samples(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
-                             uint64_t seed, uint32_t rank, uint32_t world, uint32_t s_begin, uint32_t s_end,
-                             double *d_out, void *stream) {
-    if (!r || !cam || !d_out) return fail(PT_ERR_INVALID, "null argument");
-    if (w == 0 || h == 0 || spp == 0) return fail(PT_ERR_INVALID, "width, height and samples_number must be > 0");
-    if (world == 0 || rank >= world) return fail(PT_ERR_INVALID, "rank must be < world");
-    if (s_begin >= s_end || s_end > spp)
-        return fail(PT_ERR_INVALID, "sample window must satisfy 0 <= s_begin < s_end <= samples_number");
-    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
+namespace {
+// One window of a rank's shard: the whole shard (tiles null), or the listed tiles of it (a listed launch, launch_render).
+static int render_shard(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
+                 uint32_t rank, uint32_t world, uint32_t s_begin, uint32_t s_end, bool listed, const uint32_t *tiles,
+                 uint32_t tile_count, double *d_out, void *stream) {
+    if (!r || !cam || !d_out || (listed && !tiles)) return fail(PT_ERR_INVALID, "null argument");
+    if (int rc = frame_refused(w, h, spp)) return rc;
+    if (int rc = rank_refused(rank, world)) return rc;
+    if (int rc = sample_window_refused(s_begin, s_end, spp)) return rc;
+    if (listed && !tile_list_ok(tiles, tile_count, shard_tiles(w, h, rank, world)))
+        return fail(PT_ERR_INVALID, "tiles must be 1 or more strictly ascending entries of the rank's tile list");
+    if (int rc = in_flight_refused(r)) return rc;
     GpuShare &g = r->gpus[0];
     HIP_TRY(hipSetDevice(g.device));
-    FrameParams P = frame_params(r, *cam, w, h, spp, seed);
-    P.rank = rank;
-    P.world = world;
-    P.compact = world > 1 ? 1 : 0;
-    P.tile_begin = 0;
-    P.tile_count = pt_shard_tiles(w, h, rank, world);
+    FrameParams P = shard_params(r, *cam, w, h, spp, seed, rank, world);
+    if (listed) P.tile_count = tile_count;  // positions of the list, which launch_render copies before it returns
     P.s_begin = s_begin;
     P.s_end = s_end;
     // any HIP stream of the renderer's (first) device, 0 being the null stream
     // as everywhere in HIP (pt_unshard_device takes the same handle, so a
     // caller's render -> gather -> unshard stays ordered)
-    if (int rc = render_on(g, P, d_out, (hipStream_t)stream)) return rc;
-    return PT_OK;
+    return render_on(g, P, d_out, (hipStream_t)stream, tiles);
+}
+}  // namespace
+
+int pt_render_device_samples(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t spp,
+                             uint64_t seed, uint32_t rank, uint32_t world, uint32_t s_begin, uint32_t s_end,
+                             double *d_out, void *stream) {
+    return render_shard(r, cam, w, h, spp, seed, rank, world, s_begin, s_end, false, nullptr, 0, d_out, stream);
 }
 
 int pt_render_device_tiles(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
                            uint32_t rank, uint32_t world, uint32_t s_begin, uint32_t s_end, const uint32_t *tiles,
                            uint32_t tile_count, double *d_out, void *stream) {
-    if (!r || !cam || !d_out || !tiles) return fail(PT_ERR_INVALID, "null argument");
-    if (w == 0 || h == 0 || spp == 0) return fail(PT_ERR_INVALID, "width, height and samples_number must be > 0");
-    if (world == 0 || rank >= world) return fail(PT_ERR_INVALID, "rank must be < world");
-    if (s_begin >= s_end || s_end > spp)
-        return fail(PT_ERR_INVALID, "sample window must satisfy 0 <= s_begin < s_end <= samples_number");
-    if (!tile_list_ok(tiles, tile_count, pt_shard_tiles(w, h, rank, world)))
-        return fail(PT_ERR_INVALID, "tiles must be 1 or more strictly ascending entries of the rank's tile list");
-    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
-    GpuShare &g = r->gpus[0];
-    HIP_TRY(hipSetDevice(g.device));
-    FrameParams P = frame_params(r, *cam, w, h, spp, seed);
-    P.rank = rank;
-    P.world = world;
-    P.compact = world > 1 ? 1 : 0;
-    P.tile_begin = 0;
-    P.tile_count = tile_count;  // positions of the list, which launch_render copies before it returns
-    P.s_begin = s_begin;
-    P.s_end = s_end;
-    return render_on(g, P, d_out, (hipStream_t)stream, tiles);
+    return render_shard(r, cam, w, h, spp, seed, rank, world, s_begin, s_end, true, tiles, tile_count, d_out, stream);
 }
 
 int pt_render_frame_device(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
                            double *d_frame, void *stream) {
     if (!r || !cam || !d_frame) return fail(PT_ERR_INVALID, "null argument");
-    if (w == 0 || h == 0 || spp == 0) return fail(PT_ERR_INVALID, "width, height and samples_number must be > 0");
-    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
+    if (int rc = frame_refused(w, h, spp)) return rc;
+    if (int rc = in_flight_refused(r)) return rc;
     GpuShare &g0 = r->gpus[0];
     HIP_TRY(hipSetDevice(g0.device));
     hipStream_t st = (hipStream_t)stream;
@@ -965,7 +1001,7 @@ int pt_render_frame_device(pt_renderer *r, const pt_camera *cam, uint32_t w, uin
     HIP_TRY(hipStreamWaitEvent(g0.stream, g0.shard_ev, 0));
     const FrameParams P = frame_params(r, *cam, w, h, spp, seed);
     if (int rc = frame_prologue(r, w, h)) return rc;
-    if (int rc = enqueue_band(r, P, d_frame, nullptr, 0, tiles_y_of(h), nullptr)) return rc;
+    if (int rc = enqueue_band(r, P, d_frame, nullptr, 0, tiles_across(h), nullptr)) return rc;
     HIP_TRY(hipSetDevice(g0.device));
     HIP_TRY(hipEventRecord(g0.shard_ev, g0.stream));
     HIP_TRY(hipStreamWaitEvent(st, g0.shard_ev, 0));
@@ -978,9 +1014,9 @@ int aov_args_refused(const pt_renderer *r, const pt_camera *cam, uint32_t w, uin
                      uint32_t world, const double *a, const double *n, const double *d) {
     if (!r || !cam) return fail(PT_ERR_INVALID, "null argument");
     if (!a && !n && !d) return fail(PT_ERR_INVALID, "at least one of the albedo, normal and depth planes must be given");
-    if (w == 0 || h == 0 || spp == 0) return fail(PT_ERR_INVALID, "width, height and samples_number must be > 0");
-    if (world == 0 || rank >= world) return fail(PT_ERR_INVALID, "rank must be < world");
-    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
+    if (int rc = frame_refused(w, h, spp)) return rc;
+    if (int rc = rank_refused(rank, world)) return rc;
+    if (int rc = in_flight_refused(r)) return rc;
     return PT_OK;
 }
 }  // namespace
@@ -992,12 +1028,7 @@ int pt_render_aov_device(pt_renderer *r, const pt_camera *cam, uint32_t w, uint3
     GpuShare &g = r->gpus[0];
     HIP_TRY(hipSetDevice(g.device));
     // the frame's own parameters (pt_render_device's): the pass reads the camera, the seed and the tile deal of them
-    FrameParams P = frame_params(r, *cam, w, h, spp, seed);
-    P.rank = rank;
-    P.world = world;
-    P.compact = world > 1 ? 1 : 0;
-    P.tile_begin = 0;
-    P.tile_count = pt_shard_tiles(w, h, rank, world);
+    FrameParams P = shard_params(r, *cam, w, h, spp, seed, rank, world);
     HIP_TRY(launch_aov(g.ds.view, P, d_albedo, d_normal, d_depth, (hipStream_t)stream));
     return PT_OK;
 }
@@ -1013,8 +1044,7 @@ int pt_render_aov(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, 
         if (host[k]) HIP_TRY(dev[k].alloc(count));
     if (int rc = pt_render_aov_device(r, cam, w, h, spp, seed, 0, 1, dev[0].p, dev[1].p, dev[2].p, r->stream())) return rc;
     HIP_TRY(hipStreamSynchronize(r->stream()));
-    for (int k = 0; k < 3; k++)
-        if (host[k]) HIP_TRY(hipMemcpy(host[k], dev[k].p, count * sizeof(double), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; k++) HIP_TRY(dev[k].download(host[k]));
     return PT_OK;
 }
 
@@ -1038,22 +1068,63 @@ int pt_encode_rgba8_device(int device, const double *d_rgb, size_t npix, uint8_t
 static_assert(PT_DENOISE_DEMODULATE == DENOISE_DEMODULATE && PT_DENOISE_MAX_ITERATIONS == DENOISE_MAX_ITERATIONS,
               "the header states the denoiser's flag and iteration limit");
 namespace {
-// the checks the device form and the host form share (the pointers are device or host memory alike)
+// Both filters behind one pair of functions: `variance` is null for the plain one, whose `sigma` is sigma_colour, and
+// the plane of the variance-guided one (pt_denoise_variance*, which refuse a null plane themselves), whose `sigma` is
+// sigma_variance.  The checks the device form and the host form share (the pointers are device or host memory alike):
 int denoise_args_refused(const double *rgb, const double *albedo, const double *normal, const double *depth,
-                         uint32_t w, uint32_t h, uint32_t iterations, double sigma_normal, double sigma_depth,
-                         double sigma_colour, uint32_t flags, const double *out) {
+                         const double *variance, uint32_t w, uint32_t h, uint32_t iterations, double sigma_normal,
+                         double sigma_depth, double sigma, uint32_t flags, const double *out) {
+    if (variance && !(sigma > 0.0)) return fail(PT_ERR_INVALID, "sigma_variance must be > 0");
     if (!rgb || !normal || !depth || !out) return fail(PT_ERR_INVALID, "null argument");
     if (flags & ~PT_DENOISE_DEMODULATE) return fail(PT_ERR_INVALID, "unknown denoise flag");
     if ((flags & PT_DENOISE_DEMODULATE) && !albedo)
         return fail(PT_ERR_INVALID, "PT_DENOISE_DEMODULATE needs the albedo plane");
-    if (w == 0 || h == 0) return fail(PT_ERR_INVALID, "width and height must be > 0");
+    if (int rc = frame_refused(w, h)) return rc;
     if (iterations < 1 || iterations > PT_DENOISE_MAX_ITERATIONS)
         return fail(PT_ERR_INVALID, "iterations must be 1.." + std::to_string(PT_DENOISE_MAX_ITERATIONS));
-    if (!(sigma_normal > 0.0) || !(sigma_depth > 0.0))
-        return fail(PT_ERR_INVALID, "sigma_normal and sigma_depth must be > 0");
-    if (!(sigma_colour >= 0.0)) return fail(PT_ERR_INVALID, "sigma_colour must be >= 0");
-    if (denoise_workspace_doubles(w, h) == 0 || (uint64_t)tiles_x_of(w) * tiles_y_of(h) > 0x7fffffffull)
+    if (int rc = sigmas_refused(sigma_normal, sigma_depth)) return rc;
+    if (!variance && !(sigma >= 0.0)) return fail(PT_ERR_INVALID, "sigma_colour must be >= 0");
+    if (denoise_workspace_doubles(w, h) == 0 || !tile_grid_ok(w, h))
         return fail(PT_ERR_INVALID, "the frame is too large to denoise in one call");
+    return PT_OK;
+}
+
+static int denoise_device(int device, const double *d_rgb, const double *d_albedo, const double *d_normal,
+                   const double *d_depth, const double *d_variance, uint32_t w, uint32_t h, uint32_t iterations,
+                   double sigma_normal, double sigma_depth, double sigma, uint32_t flags, double *d_out, double *d_work,
+                   void *stream) {
+    if (int rc = denoise_args_refused(d_rgb, d_albedo, d_normal, d_depth, d_variance, w, h, iterations, sigma_normal,
+                                      sigma_depth, sigma, flags, d_out))
+        return rc;
+    if (int rc = workspace_refused(d_work)) return rc;
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    const dev::DenoiseConsts k = denoise_consts(iterations, sigma_normal, sigma_depth, d_variance ? 0.0 : sigma);
+    if (d_variance)
+        HIP_TRY(launch_denoise_variance(d_rgb, d_albedo, d_normal, d_depth, d_variance, w, h, iterations, k,
+                                        denoise_variance_rv(sigma), flags, d_out, d_work, (hipStream_t)stream));
+    else
+        HIP_TRY(launch_denoise(d_rgb, d_albedo, d_normal, d_depth, w, h, iterations, k, flags, d_out, d_work,
+                               (hipStream_t)stream));
+    return PT_OK;
+}
+
+static int denoise_host(int device, const double *rgb, const double *albedo, const double *normal, const double *depth,
+                 const double *variance, uint32_t w, uint32_t h, uint32_t iterations, double sigma_normal,
+                 double sigma_depth, double sigma, uint32_t flags, double *out) {
+    if (int rc = denoise_args_refused(rgb, albedo, normal, depth, variance, w, h, iterations, sigma_normal, sigma_depth,
+                                      sigma, flags, out))
+        return rc;
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    const size_t count = (size_t)w * h * 3;
+    const double *host[5] = {rgb, (flags & PT_DENOISE_DEMODULATE) ? albedo : nullptr, normal, depth, variance};
+    DevBuf<double> dev[5], work;  // staging, freed on return; the frame is denoised in place in dev[0]
+    for (int k = 0; k < 5; k++) HIP_TRY(dev[k].upload(host[k], count));
+    HIP_TRY(work.alloc(denoise_workspace_doubles(w, h)));
+    if (int rc = denoise_device(-1, dev[0].p, dev[1].p, dev[2].p, dev[3].p, dev[4].p, w, h, iterations, sigma_normal,
+                                sigma_depth, sigma, flags, dev[0].p, work.p, nullptr))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(dev[0].download(out));
     return PT_OK;
 }
 }  // namespace
@@ -1064,40 +1135,15 @@ int pt_denoise_device(int device, const double *d_rgb, const double *d_albedo, c
                       const double *d_depth, uint32_t w, uint32_t h, uint32_t iterations, double sigma_normal,
                       double sigma_depth, double sigma_colour, uint32_t flags, double *d_out, double *d_work,
                       void *stream) {
-    if (int rc = denoise_args_refused(d_rgb, d_albedo, d_normal, d_depth, w, h, iterations, sigma_normal, sigma_depth,
-                                      sigma_colour, flags, d_out))
-        return rc;
-    if (!d_work) return fail(PT_ERR_INVALID, "null argument");
-    if (((uintptr_t)d_work & 15u) != 0) return fail(PT_ERR_INVALID, "the workspace must be 16-byte aligned");
-    if (device >= 0) HIP_TRY(hipSetDevice(device));
-    HIP_TRY(launch_denoise(d_rgb, d_albedo, d_normal, d_depth, w, h, iterations,
-                           denoise_consts(iterations, sigma_normal, sigma_depth, sigma_colour), flags, d_out, d_work,
-                           (hipStream_t)stream));
-    return PT_OK;
+    return denoise_device(device, d_rgb, d_albedo, d_normal, d_depth, nullptr, w, h, iterations, sigma_normal,
+                          sigma_depth, sigma_colour, flags, d_out, d_work, stream);
 }
 
 int pt_denoise(int device, const double *rgb, const double *albedo, const double *normal, const double *depth,
                uint32_t w, uint32_t h, uint32_t iterations, double sigma_normal, double sigma_depth,
                double sigma_colour, uint32_t flags, double *out) {
-    if (int rc = denoise_args_refused(rgb, albedo, normal, depth, w, h, iterations, sigma_normal, sigma_depth,
-                                      sigma_colour, flags, out))
-        return rc;
-    if (device >= 0) HIP_TRY(hipSetDevice(device));
-    const size_t count = (size_t)w * h * 3;
-    const double *host[4] = {rgb, (flags & PT_DENOISE_DEMODULATE) ? albedo : nullptr, normal, depth};
-    DevBuf<double> dev[4], work;  // staging, freed on return; the frame is denoised in place in dev[0]
-    for (int k = 0; k < 4; k++)
-        if (host[k]) {
-            HIP_TRY(dev[k].alloc(count));
-            HIP_TRY(hipMemcpy(dev[k].p, host[k], count * sizeof(double), hipMemcpyHostToDevice));
-        }
-    HIP_TRY(work.alloc(denoise_workspace_doubles(w, h)));
-    if (int rc = pt_denoise_device(-1, dev[0].p, dev[1].p, dev[2].p, dev[3].p, w, h, iterations, sigma_normal,
-                                   sigma_depth, sigma_colour, flags, dev[0].p, work.p, nullptr))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    HIP_TRY(hipMemcpy(out, dev[0].p, count * sizeof(double), hipMemcpyDeviceToHost));
-    return PT_OK;
+    return denoise_host(device, rgb, albedo, normal, depth, nullptr, w, h, iterations, sigma_normal, sigma_depth,
+                        sigma_colour, flags, out);
 }
 
 // ---- temporal accumulation (pt_temporal.hpp): the last frame reprojected into a moved camera, needs no renderer ----
@@ -1108,14 +1154,13 @@ int temporal_args_refused(const double *rgb, const double *normal, const double 
                           const double *history_out, uint32_t max_count, double sigma_normal, double sigma_depth,
                           const double *out) {
     if (!rgb || !normal || !depth || !camera || !history_out || !out) return fail(PT_ERR_INVALID, "null argument");
-    if (w == 0 || h == 0) return fail(PT_ERR_INVALID, "width and height must be > 0");
+    if (int rc = frame_refused(w, h)) return rc;
     if (max_count == 0) return fail(PT_ERR_INVALID, "max_count must be > 0");
-    if (!(sigma_normal > 0.0) || !(sigma_depth > 0.0))
-        return fail(PT_ERR_INVALID, "sigma_normal and sigma_depth must be > 0");
+    if (int rc = sigmas_refused(sigma_normal, sigma_depth)) return rc;
     if ((prev_camera == nullptr) != (history_in == nullptr))
         return fail(PT_ERR_INVALID, "prev_camera and history_in are given together, or neither (the first frame)");
     const size_t doubles = temporal_history_doubles(w, h);
-    if (doubles == 0 || (uint64_t)tiles_x_of(w) * tiles_y_of(h) > 0x7fffffffull)
+    if (doubles == 0 || !tile_grid_ok(w, h))
         return fail(PT_ERR_INVALID, "the frame is too large to accumulate in one call");
     if (history_in) {
         const uintptr_t a = (uintptr_t)history_in, b = (uintptr_t)history_out, bytes = doubles * sizeof(double);
@@ -1173,21 +1218,15 @@ int pt_temporal(int device, const double *rgb, const double *normal, const doubl
     const size_t count = (size_t)w * h * 3, hist = temporal_history_doubles(w, h);
     const double *host[3] = {rgb, normal, depth};
     DevBuf<double> dev[3], hin, hout;  // staging, freed on return; the frame is written in place in dev[0]
-    for (int k = 0; k < 3; k++) {
-        HIP_TRY(dev[k].alloc(count));
-        HIP_TRY(hipMemcpy(dev[k].p, host[k], count * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (history_in) {
-        HIP_TRY(hin.alloc(hist));
-        HIP_TRY(hipMemcpy(hin.p, history_in, hist * sizeof(double), hipMemcpyHostToDevice));
-    }
+    for (int k = 0; k < 3; k++) HIP_TRY(dev[k].upload(host[k], count));
+    HIP_TRY(hin.upload(history_in, hist));  // (none on the first frame)
     HIP_TRY(hout.alloc(hist));
     if (int rc = pt_temporal_device(-1, dev[0].p, dev[1].p, dev[2].p, camera, prev_camera, w, h, hin.p, hout.p,
                                     max_count, sigma_normal, sigma_depth, dev[0].p, nullptr))
         return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
-    HIP_TRY(hipMemcpy(out, dev[0].p, count * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(history_out, hout.p, hist * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(dev[0].download(out));
+    HIP_TRY(hout.download(history_out));
     return PT_OK;
 }
 
@@ -1196,7 +1235,7 @@ namespace {
 // elements of one rank's d_out; 0 on a zero size, rank >= world, or a count whose workspace does not fit
 uint64_t variance_count(uint32_t w, uint32_t h, uint32_t rank, uint32_t world) {
     if (w == 0 || h == 0 || world == 0 || rank >= world) return 0;
-    const uint64_t count = world == 1 ? (uint64_t)w * h * 3 : (uint64_t)pt_shard_tiles(w, h, rank, world) * 768;
+    const uint64_t count = shard_elements(w, h, rank, world);
     return variance_workspace_doubles(count) ? count : 0;
 }
 
@@ -1205,19 +1244,10 @@ int variance_window_refused(const double *d_out, size_t count, uint32_t n_k, uin
     if (!d_out || !d_work || !d_variance) return fail(PT_ERR_INVALID, "null argument");
     if (count == 0 || variance_workspace_doubles(count) == 0 || (count + 255) / 256 > 0x7fffffffull)
         return fail(PT_ERR_INVALID, "count must be > 0 and fit one launch");
-    if (windows < 2 || windows > spp) return fail(PT_ERR_INVALID, "windows must be 2..samples_number");
+    if (int rc = windows_refused(windows, spp)) return rc;
     if (window < 1 || window > windows) return fail(PT_ERR_INVALID, "window must be 1..windows");
     if (n_k < 1 || n_k > spp) return fail(PT_ERR_INVALID, "n_k must be 1..samples_number");
     return PT_OK;
-}
-
-int denoise_variance_refused(const double *rgb, const double *albedo, const double *normal, const double *depth,
-                             const double *variance, uint32_t w, uint32_t h, uint32_t iterations, double sigma_normal,
-                             double sigma_depth, double sigma_variance, uint32_t flags, const double *out) {
-    if (!variance) return fail(PT_ERR_INVALID, "null argument");
-    if (!(sigma_variance > 0.0)) return fail(PT_ERR_INVALID, "sigma_variance must be > 0");
-    return denoise_args_refused(rgb, albedo, normal, depth, w, h, iterations, sigma_normal, sigma_depth, 0.0, flags,
-                                out);
 }
 }  // namespace
 
@@ -1238,13 +1268,13 @@ int pt_render_variance_device(pt_renderer *r, const pt_camera *cam, uint32_t w, 
                               uint64_t seed, uint32_t rank, uint32_t world, uint32_t windows, double *d_out,
                               double *d_variance, double *d_work, void *stream) {
     if (!r || !cam || !d_out || !d_variance || !d_work) return fail(PT_ERR_INVALID, "null argument");
-    if (w == 0 || h == 0 || spp == 0) return fail(PT_ERR_INVALID, "width, height and samples_number must be > 0");
-    if (world == 0 || rank >= world) return fail(PT_ERR_INVALID, "rank must be < world");
-    if (windows < 2 || windows > spp) return fail(PT_ERR_INVALID, "windows must be 2..samples_number");
+    if (int rc = frame_refused(w, h, spp)) return rc;
+    if (int rc = rank_refused(rank, world)) return rc;
+    if (int rc = windows_refused(windows, spp)) return rc;
     const uint64_t count = variance_count(w, h, rank, world);
     if (count == 0 || (count + 255) / 256 > 0x7fffffffull)
         return fail(PT_ERR_INVALID, "the frame is too large for the variance pass (or the rank has no tile)");
-    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
+    if (int rc = in_flight_refused(r)) return rc;
     // the frame's own windows, each followed by its accumulate launch on the same stream: no sync of ours
     for (uint32_t k = 1; k <= windows; k++) {
         const uint32_t e0 = variance_edge(k - 1, spp, windows), e1 = variance_edge(k, spp, windows);
@@ -1259,11 +1289,11 @@ int pt_render_variance_device(pt_renderer *r, const pt_camera *cam, uint32_t w, 
 int pt_render_variance(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
                        uint32_t windows, double *rgb, double *variance) {
     if (!r || !cam || !rgb || !variance) return fail(PT_ERR_INVALID, "null argument");
-    if (w == 0 || h == 0 || spp == 0) return fail(PT_ERR_INVALID, "width, height and samples_number must be > 0");
-    if (windows < 2 || windows > spp) return fail(PT_ERR_INVALID, "windows must be 2..samples_number");
+    if (int rc = frame_refused(w, h, spp)) return rc;
+    if (int rc = windows_refused(windows, spp)) return rc;
     const uint64_t count = variance_count(w, h, 0, 1);
     if (count == 0) return fail(PT_ERR_INVALID, "the frame is too large for the variance pass");
-    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
+    if (int rc = in_flight_refused(r)) return rc;
     HIP_TRY(hipSetDevice(r->device()));
     DevBuf<double> out, var, work;  // staging, freed on return
     HIP_TRY(out.alloc((size_t)count));
@@ -1272,8 +1302,8 @@ int pt_render_variance(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_
     if (int rc = pt_render_variance_device(r, cam, w, h, spp, seed, 0, 1, windows, out.p, var.p, work.p, r->stream()))
         return rc;
     HIP_TRY(hipStreamSynchronize(r->stream()));
-    HIP_TRY(hipMemcpy(rgb, out.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(variance, var.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(out.download(rgb));
+    HIP_TRY(var.download(variance));
     return PT_OK;
 }
 
@@ -1281,41 +1311,17 @@ int pt_denoise_variance_device(int device, const double *d_rgb, const double *d_
                                const double *d_depth, const double *d_variance, uint32_t w, uint32_t h,
                                uint32_t iterations, double sigma_normal, double sigma_depth, double sigma_variance,
                                uint32_t flags, double *d_out, double *d_work, void *stream) {
-    if (int rc = denoise_variance_refused(d_rgb, d_albedo, d_normal, d_depth, d_variance, w, h, iterations,
-                                          sigma_normal, sigma_depth, sigma_variance, flags, d_out))
-        return rc;
-    if (!d_work) return fail(PT_ERR_INVALID, "null argument");
-    if (((uintptr_t)d_work & 15u) != 0) return fail(PT_ERR_INVALID, "the workspace must be 16-byte aligned");
-    if (device >= 0) HIP_TRY(hipSetDevice(device));
-    HIP_TRY(launch_denoise_variance(d_rgb, d_albedo, d_normal, d_depth, d_variance, w, h, iterations,
-                                    denoise_consts(iterations, sigma_normal, sigma_depth, 0.0),
-                                    denoise_variance_rv(sigma_variance), flags, d_out, d_work, (hipStream_t)stream));
-    return PT_OK;
+    if (!d_variance) return fail(PT_ERR_INVALID, "null argument");
+    return denoise_device(device, d_rgb, d_albedo, d_normal, d_depth, d_variance, w, h, iterations, sigma_normal,
+                          sigma_depth, sigma_variance, flags, d_out, d_work, stream);
 }
 
 int pt_denoise_variance(int device, const double *rgb, const double *albedo, const double *normal,
                         const double *depth, const double *variance, uint32_t w, uint32_t h, uint32_t iterations,
                         double sigma_normal, double sigma_depth, double sigma_variance, uint32_t flags, double *out) {
-    if (int rc = denoise_variance_refused(rgb, albedo, normal, depth, variance, w, h, iterations, sigma_normal,
-                                          sigma_depth, sigma_variance, flags, out))
-        return rc;
-    if (device >= 0) HIP_TRY(hipSetDevice(device));
-    const size_t count = (size_t)w * h * 3;
-    const double *host[5] = {rgb, (flags & PT_DENOISE_DEMODULATE) ? albedo : nullptr, normal, depth, variance};
-    DevBuf<double> dev[5], work;  // staging, freed on return; the frame is denoised in place in dev[0]
-    for (int k = 0; k < 5; k++)
-        if (host[k]) {
-            HIP_TRY(dev[k].alloc(count));
-            HIP_TRY(hipMemcpy(dev[k].p, host[k], count * sizeof(double), hipMemcpyHostToDevice));
-        }
-    HIP_TRY(work.alloc(denoise_workspace_doubles(w, h)));
-    if (int rc = pt_denoise_variance_device(-1, dev[0].p, dev[1].p, dev[2].p, dev[3].p, dev[4].p, w, h, iterations,
-                                            sigma_normal, sigma_depth, sigma_variance, flags, dev[0].p, work.p,
-                                            nullptr))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    HIP_TRY(hipMemcpy(out, dev[0].p, count * sizeof(double), hipMemcpyDeviceToHost));
-    return PT_OK;
+    if (!variance) return fail(PT_ERR_INVALID, "null argument");
+    return denoise_host(device, rgb, albedo, normal, depth, variance, w, h, iterations, sigma_normal, sigma_depth,
+                        sigma_variance, flags, out);
 }
 
 // ---- adaptive sampling: every tile stops at a noise target (pt_adaptive.hpp) ----
@@ -1333,8 +1339,8 @@ int adaptive_refused(const void *r, const void *cam, uint32_t w, uint32_t h, uin
     if (min_samples > max_samples) return fail(PT_ERR_INVALID, "min_samples must be at most max_samples");
     if (!(threshold >= 0.0)) return fail(PT_ERR_INVALID, "threshold must be >= 0");
     if (!(luminance_floor >= 0.0)) return fail(PT_ERR_INVALID, "luminance_floor must be >= 0");
-    if (world == 0 || rank >= world) return fail(PT_ERR_INVALID, "rank must be < world");
-    if (pt_shard_tiles(w, h, rank, world) == 0 || adaptive_workspace_doubles(variance_count(w, h, rank, world)) == 0)
+    if (int rc = rank_refused(rank, world)) return rc;
+    if (shard_tiles(w, h, rank, world) == 0 || adaptive_workspace_doubles(variance_count(w, h, rank, world)) == 0)
         return fail(PT_ERR_INVALID, "the frame is too large for the adaptive pass (or the rank has no tile)");
     return PT_OK;
 }
@@ -1355,22 +1361,18 @@ int adaptive_device(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h
     if (int rc = adaptive_refused(r, cam, w, h, window, min_samples, max_samples, threshold, luminance_floor, rank,
                                   world, d_out, d_tile_samples))
         return rc;
-    if (!d_work) return fail(PT_ERR_INVALID, "null argument");
-    if (((uintptr_t)d_work & 15u) != 0) return fail(PT_ERR_INVALID, "the workspace must be 16-byte aligned");
-    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
+    if (int rc = workspace_refused(d_work)) return rc;
+    if (int rc = in_flight_refused(r)) return rc;
     GpuShare &g = r->gpus[0];
     HIP_TRY(hipSetDevice(g.device));
     hipStream_t st = (hipStream_t)stream;
     const size_t count = (size_t)variance_count(w, h, rank, world);
-    const uint32_t ntiles = pt_shard_tiles(w, h, rank, world);
+    const uint32_t ntiles = shard_tiles(w, h, rank, world);
     // Every window is a window of a frame one sample longer than the cap, so s_end < spp always holds and the render
     // leaves sums, never means: spp reaches only wf_reduce's final division and the engine choice (a windowed frame
     // always runs the wavefront engine; the samples' keys come from their indices).
-    FrameParams P = frame_params(r, *cam, w, h, max_samples + 1, seed);
-    P.rank = rank;
-    P.world = world;
-    P.compact = world > 1 ? 1 : 0;
-    const dev::AdaptiveGeom geom{w, h, rank, world, P.tiles_x, P.compact};
+    FrameParams P = shard_params(r, *cam, w, h, max_samples + 1, seed, rank, world);
+    const dev::AdaptiveGeom geom{dev::tile_geom(P)};
     std::vector<uint8_t> active(ntiles, 1);
     std::vector<uint32_t> pixels(ntiles), stopped(ntiles);
     for (uint32_t i = 0; i < ntiles; i++) pixels[i] = dev::adaptive_tile_pixels(geom, i);
@@ -1422,9 +1424,9 @@ int adaptive_host(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, 
     if (int rc = adaptive_refused(r, cam, w, h, window, min_samples, max_samples, threshold, luminance_floor, 0, 1,
                                   rgb, tile_samples))
         return rc;
-    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
+    if (int rc = in_flight_refused(r)) return rc;
     HIP_TRY(hipSetDevice(r->device()));
-    const size_t count = (size_t)w * h * 3, ntiles = pt_shard_tiles(w, h, 0, 1);
+    const size_t count = (size_t)w * h * 3, ntiles = shard_tiles(w, h, 0, 1);
     DevBuf<double> out, var, err, work;  // staging, freed on return
     DevBuf<uint32_t> ts;
     HIP_TRY(out.alloc(count));
@@ -1436,10 +1438,10 @@ int adaptive_host(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, 
     if (int rc = adaptive_device(r, cam, w, h, window, min_samples, max_samples, threshold, luminance_floor, listed,
                                  merge_gap, seed, 0, 1, out.p, var.p, ts.p, err.p, work.p, r->stream(), &launched))
         return rc;
-    HIP_TRY(hipMemcpy(rgb, out.p, count * sizeof(double), hipMemcpyDeviceToHost));
-    if (variance) HIP_TRY(hipMemcpy(variance, var.p, count * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(tile_samples, ts.p, ntiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (tile_error) HIP_TRY(hipMemcpy(tile_error, err.p, ntiles * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(out.download(rgb));
+    HIP_TRY(var.download(variance));
+    HIP_TRY(ts.download(tile_samples));
+    HIP_TRY(err.download(tile_error));
     if (samples_rendered) *samples_rendered = launched;
     return PT_OK;
 }
@@ -1488,12 +1490,11 @@ int pt_closest_hit(pt_renderer *r, const double *rays, size_t n, double min_t, d
     HIP_TRY(hipSetDevice(r->device()));
     DevBuf<double> dr;
     DevBuf<pt_hit> dh;
-    HIP_TRY(dr.alloc(n * 6));
+    HIP_TRY(dr.upload(rays, n * 6));
     HIP_TRY(dh.alloc(n));
-    HIP_TRY(hipMemcpy(dr.p, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(launch_closest_hit(r->gpus[0].ds, dr.p, n, min_t, max_t, dh.p, r->stream()));
     HIP_TRY(hipStreamSynchronize(r->stream()));
-    HIP_TRY(hipMemcpy(out, dh.p, n * sizeof(pt_hit), hipMemcpyDeviceToHost));
+    HIP_TRY(dh.download(out));
     return PT_OK;
 }
 
@@ -1503,35 +1504,38 @@ int pt_ray_color(pt_renderer *r, const double *rays, uint64_t *states, size_t n,
     HIP_TRY(hipSetDevice(r->device()));
     DevBuf<double> dr, dout;
     DevBuf<uint64_t> ds;
-    HIP_TRY(dr.alloc(n * 6));
-    HIP_TRY(ds.alloc(n));
+    HIP_TRY(dr.upload(rays, n * 6));
+    HIP_TRY(ds.upload(states, n));
     HIP_TRY(dout.alloc(n * 3));
-    HIP_TRY(hipMemcpy(dr.p, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ds.p, states, n * sizeof(uint64_t), hipMemcpyHostToDevice));
     HIP_TRY(launch_ray_color(r->gpus[0].ds, dr.p, ds.p, n, depth, r->s11, dout.p, r->stream()));
     HIP_TRY(hipStreamSynchronize(r->stream()));
-    HIP_TRY(hipMemcpy(out, dout.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(states, ds.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(dout.download(out));
+    HIP_TRY(ds.download(states));
     return PT_OK;
+}
+
+// the checks of the two probes that trace listed pixels, after their null checks
+static int pixel_probe_refused(const pt_renderer *r, uint32_t w, uint32_t h, uint32_t spp, const uint32_t *pixels,
+                               size_t n, const char *call) {
+    if (int rc = frame_refused(w, h, spp)) return rc;
+    for (size_t i = 0; i < n; i++)
+        if (pixels[i] >= (uint64_t)w * h) return fail(PT_ERR_INVALID, "pixel index out of range");
+    return reg_depth_refused(r->depth, call);
 }
 
 int pt_trace_pixel_samples(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
                            const uint32_t *pixels, size_t n, double *out) {
     if (!r || !cam || (n && (!pixels || !out))) return fail(PT_ERR_INVALID, "null argument");
-    if (w == 0 || h == 0 || spp == 0) return fail(PT_ERR_INVALID, "width, height and samples_number must be > 0");
-    for (size_t i = 0; i < n; i++)
-        if (pixels[i] >= (uint64_t)w * h) return fail(PT_ERR_INVALID, "pixel index out of range");
-    if (int rc = reg_depth_refused(r->depth, "pt_trace_pixel_samples")) return rc;
+    if (int rc = pixel_probe_refused(r, w, h, spp, pixels, n, "pt_trace_pixel_samples")) return rc;
     HIP_TRY(hipSetDevice(r->device()));
     FrameParams P = frame_params(r, *cam, w, h, spp, seed);
     DevBuf<uint32_t> dp;
     DevBuf<double> dout;
-    HIP_TRY(dp.alloc(n));
+    HIP_TRY(dp.upload(pixels, n));
     HIP_TRY(dout.alloc(n * 3));
-    HIP_TRY(hipMemcpy(dp.p, pixels, n * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(launch_trace_pixels(r->gpus[0].ds, P, dp.p, n, dout.p, r->stream()));
     HIP_TRY(hipStreamSynchronize(r->stream()));
-    HIP_TRY(hipMemcpy(out, dout.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(dout.download(out));
     return PT_OK;
 }
 
@@ -1539,21 +1543,17 @@ int pt_count_work(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t h, 
                   const uint32_t *pixels, size_t n, uint64_t *counters) {
     static_assert(C_COUNT == PT_NUM_COUNTERS, "counter list matches the header");
     if (!r || !cam || !counters || (n && !pixels)) return fail(PT_ERR_INVALID, "null argument");
-    if (w == 0 || h == 0 || spp == 0) return fail(PT_ERR_INVALID, "width, height and samples_number must be > 0");
-    for (size_t i = 0; i < n; i++)
-        if (pixels[i] >= (uint64_t)w * h) return fail(PT_ERR_INVALID, "pixel index out of range");
-    if (int rc = reg_depth_refused(r->depth, "pt_count_work")) return rc;
+    if (int rc = pixel_probe_refused(r, w, h, spp, pixels, n, "pt_count_work")) return rc;
     HIP_TRY(hipSetDevice(r->device()));
     FrameParams P = frame_params(r, *cam, w, h, spp, seed);
     DevBuf<uint32_t> dp;
     DevBuf<unsigned long long> dc;
-    HIP_TRY(dp.alloc(n));
+    HIP_TRY(dp.upload(pixels, n));
     HIP_TRY(dc.alloc(C_COUNT));
-    HIP_TRY(hipMemcpy(dp.p, pixels, n * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(dc.p, 0, C_COUNT * sizeof(unsigned long long), r->stream()));
     HIP_TRY(launch_count_work(r->gpus[0].ds, P, dp.p, n, dc.p, r->stream()));
     HIP_TRY(hipStreamSynchronize(r->stream()));
-    HIP_TRY(hipMemcpy(counters, dc.p, C_COUNT * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(dc.download((unsigned long long *)counters));
     return PT_OK;
 }
 
@@ -1577,44 +1577,41 @@ int pt_march_jobs(pt_renderer *r, const double *jobs, size_t n, double *t_out, i
     return PT_OK;
 }
 
-int pt_march_guard_drops(pt_renderer *r, uint64_t *count) {
-    if (!r || !count) return fail(PT_ERR_INVALID, "null argument");
-    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
-    uint64_t total = 0;
+namespace {
+// Device counters [first, first + n) of every device (init_share lists them), summed into out and cleared.
+static int drain_counters(pt_renderer *r, int first, int n, uint64_t *out) {
+    if (int rc = in_flight_refused(r)) return rc;
+    unsigned long long c[2], total[2] = {0, 0};
     for (auto &g : r->gpus) {
         HIP_TRY(hipSetDevice(g.device));
         HIP_TRY(hipDeviceSynchronize());  // frames on any stream of the device
-        unsigned long long n = 0;
-        HIP_TRY(hipMemcpy(&n, g.ds.view.guard, sizeof n, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemset(g.ds.view.guard, 0, sizeof n));
-        total += n;
+        HIP_TRY(hipMemcpy(c, g.ds.view.guard + first, n * sizeof *c, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemset(g.ds.view.guard + first, 0, n * sizeof *c));
+        for (int k = 0; k < n; k++) total[k] += c[k];
     }
-    *count = total;
+    for (int k = 0; k < n; k++) out[k] = total[k];
     return PT_OK;
+}
+}  // namespace
+
+int pt_march_guard_drops(pt_renderer *r, uint64_t *count) {
+    if (!r || !count) return fail(PT_ERR_INVALID, "null argument");
+    return drain_counters(r, 0, 1, count);
 }
 
 int pt_render_stop_stats(pt_renderer *r, uint64_t *skipped, uint64_t *worked) {
     if (!r || !skipped || !worked) return fail(PT_ERR_INVALID, "null argument");
-    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
-    uint64_t s = 0, w = 0;
-    for (auto &g : r->gpus) {
-        HIP_TRY(hipSetDevice(g.device));
-        HIP_TRY(hipDeviceSynchronize());
-        unsigned long long c[2] = {0, 0};
-        HIP_TRY(hipMemcpy(c, g.ds.view.guard + 1, sizeof c, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemset(g.ds.view.guard + 1, 0, sizeof c));
-        s += c[0];
-        w += c[1];
-    }
-    *skipped = s;
-    *worked = w;
+    uint64_t c[2];
+    if (int rc = drain_counters(r, 1, 2, c)) return rc;
+    *skipped = c[0];
+    *worked = c[1];
     return PT_OK;
 }
 
 int pt_kernel_timing(pt_renderer *r, int enable, double *ms, uint32_t *launches, size_t nkinds) {
     if (!r) return fail(PT_ERR_INVALID, "null argument");
     // the band feeder pushes into the timer and may queue timed launches
-    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
+    if (int rc = in_flight_refused(r)) return rc;
     HIP_TRY(hipSetDevice(r->device()));
     double m[K_KINDS];
     uint32_t l[K_KINDS];
@@ -1634,7 +1631,7 @@ int pt_kernel_timing(pt_renderer *r, int enable, double *ms, uint32_t *launches,
 int pt_wave_diag(pt_renderer *r, int enable, uint64_t *out, size_t n) {
     if (!r) return fail(PT_ERR_INVALID, "null argument");
     // the band feeder may queue launches that use the diag buffer
-    if (r->started) return fail(PT_ERR_STATE, "a progressive frame is in flight (render_step it to the end or stop it)");
+    if (int rc = in_flight_refused(r)) return rc;
     if (enable && !PT_WAVE_DIAG)
         return fail(PT_ERR_UNSUPPORTED, "wave diagnostics are compiled out of this build (make EXTRA=-DPT_WAVE_DIAG=1)");
     HIP_TRY(hipSetDevice(r->device()));
@@ -1654,8 +1651,7 @@ int pt_profile_phases(pt_renderer *r, const pt_camera *cam, uint32_t w, uint32_t
     if (!r || !cam || !out) return fail(PT_ERR_INVALID, "null argument");
     if (r->depth > 8) return fail(PT_ERR_UNSUPPORTED, "phase profiling supports depth <= 8");
     HIP_TRY(hipSetDevice(r->device()));
-    FrameParams P = frame_params(r, *cam, w, h, spp, seed);
-    P.tile_count = pt_shard_tiles(w, h, 0, 1);
+    const FrameParams P = shard_params(r, *cam, w, h, spp, seed, 0, 1);
     DevBuf<double> frame;
     DevBuf<unsigned long long> acc;
     HIP_TRY(frame.alloc((size_t)w * h * 3));

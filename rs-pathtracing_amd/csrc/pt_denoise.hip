@@ -4,7 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pt_denoise.hpp"
-#include "pt_dims.hpp"
+#include "pt_tiles.hpp"
 
 namespace pt {
 
@@ -19,7 +19,7 @@ __global__ __launch_bounds__(256) void denoise_records(const double *__restrict_
     if (p < npix) dev::denoise_prepare(rgb, albedo, normal, depth, flags, p, u, g);
 }
 
-// One iteration.  aov_tiles' geometry: one workgroup = one 16x16 tile, 4 wave64s of 8x8 pixels, one pixel per lane,
+// One iteration.  The whole frame in pt_tiles.hpp's geometry: one workgroup = one 16x16 tile, 8x8 pixels per wave64,
 // so each tap row of a wave is one contiguous run of 8 records (256 bytes), and every tap is 16-byte loads.  The
 // stride is a kernel argument; the colour term is a template argument (off, the default, does not pay for xc);
 // LAST fuses the remodulation and writes the frame instead of the next colour buffer.
@@ -32,52 +32,14 @@ __global__ __launch_bounds__(256) void denoise_tiles(const DRec *__restrict__ u,
                                                      double rz, double rc, DRec *__restrict__ u_next,
                                                      const double *__restrict__ albedo, uint32_t flags,
                                                      double *__restrict__ out) {
-    const uint32_t tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-    const uint32_t wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-    const uint32_t lx = ((wv & 1u) << 3) | (l & 7u), ly = ((wv >> 1) << 3) | (l >> 3);
-    const uint32_t x = tx * TILE + lx, y = ty * TILE + ly;
-    if (x >= w || y >= h) return;
+    const dev::LanePixel lp = dev::lane_pixel(threadIdx.x);
+    const dev::TilePixel px = dev::tile_pixel(dev::whole_frame(w, h, tiles_x), blockIdx.x, lp.lx, lp.ly);
+    if (!px.inside) return;
+    const uint32_t x = px.x, y = px.y;
     const DRec v = dev::denoise_pixel<COLOUR>(u, g, w, h, x, y, s, rn, rz, rc);
     const size_t p = (size_t)y * w + x;
     if (LAST) dev::denoise_finish(v, albedo, flags, p, out);
     else u_next[p] = v;
-}
-
-template <bool COLOUR>
-static hipError_t launch_iterations(const double *albedo, uint32_t w, uint32_t h, uint32_t iterations,
-                                    const dev::DenoiseConsts &k, uint32_t flags, double *out, DRec *u0, DRec *u1,
-                                    const DRec *g, hipStream_t st) {
-    const uint32_t tiles_x = (w + TILE - 1) / TILE, tiles_y = (h + TILE - 1) / TILE;
-    const uint32_t tiles = tiles_x * tiles_y;
-    for (uint32_t i = 0; i < iterations; i++) {
-        const DRec *src = i & 1u ? u1 : u0;
-        DRec *dst = i & 1u ? u0 : u1;
-        if (i + 1 < iterations)
-            denoise_tiles<COLOUR, false><<<tiles, 256, 0, st>>>(src, g, w, h, tiles_x, 1u << i, k.rn, k.rz, k.rc[i], dst,
-                                                                nullptr, flags, nullptr);
-        else
-            denoise_tiles<COLOUR, true><<<tiles, 256, 0, st>>>(src, g, w, h, tiles_x, 1u << i, k.rn, k.rz, k.rc[i],
-                                                               nullptr, albedo, flags, out);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-hipError_t launch_denoise(const double *rgb, const double *albedo, const double *normal, const double *depth,
-                          uint32_t w, uint32_t h, uint32_t iterations, const dev::DenoiseConsts &k, uint32_t flags,
-                          double *out, double *work, hipStream_t st) {
-    const size_t npix = (size_t)w * h;
-    // the tile grid and the prepare grid are 32-bit
-    const uint64_t tiles = (uint64_t)((w + TILE - 1) / TILE) * ((h + TILE - 1) / TILE);
-    if (npix == 0 || iterations == 0 || iterations > DENOISE_MAX_ITERATIONS || tiles > 0x7fffffffull)
-        return hipErrorInvalidValue;
-    DRec *u0 = (DRec *)work, *u1 = u0 + npix, *g = u1 + npix;
-    denoise_records<<<(unsigned)((npix + 255) / 256), 256, 0, st>>>(rgb, albedo, normal, depth, flags, npix, u0, g);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return k.colour ? launch_iterations<true>(albedo, w, h, iterations, k, flags, out, u0, u1, g, st)
-                    : launch_iterations<false>(albedo, w, h, iterations, k, flags, out, u0, u1, g, st);
 }
 
 // ---- the variance term (pt_denoise.hpp): kernels of its own beside the ones above ----
@@ -99,44 +61,69 @@ __global__ __launch_bounds__(256) void denoise_tiles_variance(const DRec *__rest
                                                               DRec *__restrict__ u_next,
                                                               const double *__restrict__ albedo, uint32_t flags,
                                                               double *__restrict__ out) {
-    const uint32_t tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-    const uint32_t wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-    const uint32_t lx = ((wv & 1u) << 3) | (l & 7u), ly = ((wv >> 1) << 3) | (l >> 3);
-    const uint32_t x = tx * TILE + lx, y = ty * TILE + ly;
-    if (x >= w || y >= h) return;
+    const dev::LanePixel lp = dev::lane_pixel(threadIdx.x);
+    const dev::TilePixel px = dev::tile_pixel(dev::whole_frame(w, h, tiles_x), blockIdx.x, lp.lx, lp.ly);
+    if (!px.inside) return;
+    const uint32_t x = px.x, y = px.y;
     const DRec v = dev::denoise_pixel_variance(u, g, w, h, x, y, s, rn, rz, rv);
     const size_t p = (size_t)y * w + x;
     if (LAST) dev::denoise_finish(v, albedo, flags, p, out);
     else u_next[p] = v;
 }
 
-hipError_t launch_denoise_variance(const double *rgb, const double *albedo, const double *normal, const double *depth,
-                                   const double *variance, uint32_t w, uint32_t h, uint32_t iterations,
-                                   const dev::DenoiseConsts &k, double rv, uint32_t flags, double *out, double *work,
-                                   hipStream_t st) {
+// Both filters: the frame's records, then `iterations` launches that ping-pong the colour buffer, the last of which
+// writes the frame.  variance is null for the plain filter (its colour term as k.colour says), else the plane of the
+// variance-guided one, whose every iteration takes rv where the plain filter takes k.rc[i].
+using TilesKernel = void (*)(const DRec *, const DRec *, uint32_t, uint32_t, uint32_t, uint32_t, double, double, double,
+                             DRec *, const double *, uint32_t, double *);
+static hipError_t launch_filter(const double *rgb, const double *albedo, const double *normal, const double *depth,
+                                const double *variance, uint32_t w, uint32_t h, uint32_t iterations,
+                                const dev::DenoiseConsts &k, double rv, uint32_t flags, double *out, double *work,
+                                hipStream_t st) {
     const size_t npix = (size_t)w * h;
-    const uint32_t tiles_x = (w + TILE - 1) / TILE, tiles_y = (h + TILE - 1) / TILE;
-    const uint64_t tiles = (uint64_t)tiles_x * tiles_y;
-    if (npix == 0 || iterations == 0 || iterations > DENOISE_MAX_ITERATIONS || tiles > 0x7fffffffull)
+    // the tile grid and the prepare grid are 32-bit
+    if (npix == 0 || iterations == 0 || iterations > DENOISE_MAX_ITERATIONS || !tile_grid_ok(w, h))
         return hipErrorInvalidValue;
+    const uint32_t tiles_x = tiles_across(w), tiles = tiles_x * tiles_across(h);
     DRec *u0 = (DRec *)work, *u1 = u0 + npix, *g = u1 + npix;
-    denoise_records_variance<<<(unsigned)((npix + 255) / 256), 256, 0, st>>>(rgb, albedo, normal, depth, variance, flags,
-                                                                             npix, u0, g);
+    const unsigned blocks = (unsigned)((npix + 255) / 256);
+    if (variance)
+        denoise_records_variance<<<blocks, 256, 0, st>>>(rgb, albedo, normal, depth, variance, flags, npix, u0, g);
+    else
+        denoise_records<<<blocks, 256, 0, st>>>(rgb, albedo, normal, depth, flags, npix, u0, g);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    static const TilesKernel tiles_kernel[3][2] = {  // [filter][the last iteration]
+        {denoise_tiles<true, false>, denoise_tiles<true, true>},
+        {denoise_tiles<false, false>, denoise_tiles<false, true>},
+        {denoise_tiles_variance<false>, denoise_tiles_variance<true>}};
+    const TilesKernel *const kernel = tiles_kernel[variance ? 2 : k.colour ? 0 : 1];
     for (uint32_t i = 0; i < iterations; i++) {
         const DRec *src = i & 1u ? u1 : u0;
         DRec *dst = i & 1u ? u0 : u1;
+        const double r = variance ? rv : k.rc[i];
         if (i + 1 < iterations)
-            denoise_tiles_variance<false><<<(unsigned)tiles, 256, 0, st>>>(src, g, w, h, tiles_x, 1u << i, k.rn, k.rz, rv,
-                                                                           dst, nullptr, flags, nullptr);
+            kernel[0]<<<tiles, 256, 0, st>>>(src, g, w, h, tiles_x, 1u << i, k.rn, k.rz, r, dst, nullptr, flags, nullptr);
         else
-            denoise_tiles_variance<true><<<(unsigned)tiles, 256, 0, st>>>(src, g, w, h, tiles_x, 1u << i, k.rn, k.rz, rv,
-                                                                          nullptr, albedo, flags, out);
+            kernel[1]<<<tiles, 256, 0, st>>>(src, g, w, h, tiles_x, 1u << i, k.rn, k.rz, r, nullptr, albedo, flags, out);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+hipError_t launch_denoise(const double *rgb, const double *albedo, const double *normal, const double *depth,
+                          uint32_t w, uint32_t h, uint32_t iterations, const dev::DenoiseConsts &k, uint32_t flags,
+                          double *out, double *work, hipStream_t st) {
+    return launch_filter(rgb, albedo, normal, depth, nullptr, w, h, iterations, k, 0.0, flags, out, work, st);
+}
+
+hipError_t launch_denoise_variance(const double *rgb, const double *albedo, const double *normal, const double *depth,
+                                   const double *variance, uint32_t w, uint32_t h, uint32_t iterations,
+                                   const dev::DenoiseConsts &k, double rv, uint32_t flags, double *out, double *work,
+                                   hipStream_t st) {
+    if (!variance) return hipErrorInvalidValue;
+    return launch_filter(rgb, albedo, normal, depth, variance, w, h, iterations, k, rv, flags, out, work, st);
 }
 
 }  // namespace pt

@@ -1,6 +1,6 @@
 // pt_denoise.hpp — the guided denoiser for a beauty frame and its guide planes: an edge-avoiding
 // à-trous wavelet filter (Dammertz et al. 2010) in f64, with no transcendental function and a fixed summation
-// order, so the GPU, the host build (tests/native/denoise.mk) and the numpy restatement (tests/denoiseref.py) give
+// order, so the GPU, the host build (tests/native/Makefile) and the numpy restatement (tests/denoiseref.py) give
 // the same bits.  A pass of its own: it reads four whole frames in the colour buffer's layout (world == 1), knows
 // nothing of scenes or renderers, and the render kernels do not know about it.
 //
@@ -26,9 +26,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#ifndef PT_HD
-#define PT_HD __host__ __device__ __forceinline__
-#endif
+#include "pt_dims.hpp"
 
 namespace pt {
 

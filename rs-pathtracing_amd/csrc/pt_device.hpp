@@ -13,6 +13,7 @@
 
 #include "pt_lprof.hpp"
 #include "pt_march.hpp"
+#include "pt_tiles.hpp"
 #include "pt_torus.hpp"
 #include "pt_types.hpp"
 
@@ -309,21 +310,6 @@ PT_HD DBox uniform_box(const DBox *p) {
         b.hi[k] = uniform_load(&p->hi[k]);
     }
     return b;
-}
-
-// Multi-rank tile deal (world > 1): rank r owns logical tiles k = r + i*world;
-// logical tile k sits at column (k % tiles_x + row) % tiles_x of its row, so a
-// rank's columns shift by one per row (a diagonal deal) instead of repeating
-// in every row when tiles_x is a multiple of world.  world == 1: identity.
-PT_HD uint32_t tile_position(uint32_t k, uint32_t tiles_x, uint32_t world) {
-    if (world <= 1) return k;
-    const uint32_t ty = k / tiles_x;
-    return ty * tiles_x + (k % tiles_x + ty) % tiles_x;
-}
-PT_HD uint32_t tile_logical(uint32_t p, uint32_t tiles_x, uint32_t world) {
-    if (world <= 1) return p;
-    const uint32_t ty = p / tiles_x;
-    return ty * tiles_x + (p % tiles_x + tiles_x - ty % tiles_x) % tiles_x;
 }
 
 // Ray i of an array of 6 doubles per ray (origin, direction), and colour i of one of 3 doubles per colour: the

@@ -4,6 +4,13 @@
 #include <cstddef>
 #include <cstdint>
 
+// A function of the device code that a test-only host build compiles too; the plain host compiler sees plain C++.
+#ifdef __HIPCC__
+#define PT_HD __host__ __device__ __forceinline__
+#else
+#define PT_HD inline
+#endif
+
 namespace pt {
 
 constexpr uint32_t TILE = 16;  // 16x16 pixels = one 256-thread workgroup

@@ -20,10 +20,6 @@
 
 #include "pt_dims.hpp"  // FuncKind, F_ANY, F_NONE
 
-#ifndef PT_HD
-#define PT_HD __host__ __device__ __forceinline__
-#endif
-
 namespace pt {
 namespace march {
 

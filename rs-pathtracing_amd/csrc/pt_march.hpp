@@ -30,10 +30,6 @@
 
 #include "pt_funcs.hpp"
 
-#ifndef PT_HD
-#define PT_HD __host__ __device__ __forceinline__
-#endif
-
 // Host-only profiling hooks (tools/march_prof.cpp); no-ops in the product.
 #ifndef PT_MPROF
 #define PT_MPROF(field) ((void)0)

@@ -3,15 +3,15 @@
 // path's identity (PT_SRC_SHA, Makefile).
 #include <hip/hip_runtime.h>
 
-#include "pt_dims.hpp"
 #include "pt_temporal.hpp"
+#include "pt_tiles.hpp"
 
 namespace pt {
 
 using dev::DRec;
 
-// The whole pass.  denoise_tiles' geometry: one workgroup = one 16x16 tile, 4 wave64s of 8x8 pixels, one pixel per
-// lane.  A small camera motion maps a wave's 8x8 pixels onto a patch of about 9x9 history pixels, so its four taps
+// The whole pass, over the whole frame in pt_tiles.hpp's geometry: one workgroup = one 16x16 tile, 8x8 pixels per
+// wave64.  A small camera motion maps a wave's 8x8 pixels onto a patch of about 9x9 history pixels, so its four taps
 // fall into a few contiguous runs of records; every record access is a 16-byte load or store, the three frames are
 // read and the frame written as 8-byte accesses of 24-byte pixels.  FIRST is the first frame: every pixel resets and
 // the previous history is not read (its pointers are null).  rgb and out may be the same buffer (each lane reads its
@@ -24,11 +24,10 @@ __global__ __launch_bounds__(256) void temporal_tiles(const double *rgb, const d
                                                       const DRec *__restrict__ hg, uint32_t w, uint32_t h,
                                                       uint32_t tiles_x, dev::TemporalConsts k, DRec *__restrict__ oc,
                                                       DRec *__restrict__ og, double *out) {
-    const uint32_t tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-    const uint32_t wv = threadIdx.x >> 6, l = threadIdx.x & 63;
-    const uint32_t lx = ((wv & 1u) << 3) | (l & 7u), ly = ((wv >> 1) << 3) | (l >> 3);
-    const uint32_t x = tx * TILE + lx, y = ty * TILE + ly;
-    if (x >= w || y >= h) return;
+    const dev::LanePixel lp = dev::lane_pixel(threadIdx.x);
+    const dev::TilePixel px = dev::tile_pixel(dev::whole_frame(w, h, tiles_x), blockIdx.x, lp.lx, lp.ly);
+    if (!px.inside) return;
+    const uint32_t x = px.x, y = px.y;
     DRec c, g;
     dev::temporal_pixel<FIRST>(rgb, normal, depth, hc, hg, w, h, x, y, k, &c, &g);
     const size_t p = (size_t)y * w + x;
@@ -43,16 +42,14 @@ hipError_t launch_temporal(const double *rgb, const double *normal, const double
                            const dev::TemporalConsts &k, const double *history_in, double *history_out, double *out,
                            hipStream_t st) {
     const size_t npix = (size_t)w * h;
-    const uint32_t tiles_x = (w + TILE - 1) / TILE, tiles_y = (h + TILE - 1) / TILE;
-    const uint64_t tiles = (uint64_t)tiles_x * tiles_y;  // the tile grid is 32-bit
-    if (npix == 0 || tiles > 0x7fffffffull) return hipErrorInvalidValue;
+    if (npix == 0 || !tile_grid_ok(w, h)) return hipErrorInvalidValue;  // the tile grid is 32-bit
+    const uint32_t tiles_x = tiles_across(w), tiles = tiles_x * tiles_across(h);
     DRec *oc = (DRec *)history_out, *og = oc + npix;
     if (history_in) {
         const DRec *hc = (const DRec *)history_in, *hg = hc + npix;
-        temporal_tiles<false><<<(unsigned)tiles, 256, 0, st>>>(rgb, normal, depth, hc, hg, w, h, tiles_x, k, oc, og, out);
+        temporal_tiles<false><<<tiles, 256, 0, st>>>(rgb, normal, depth, hc, hg, w, h, tiles_x, k, oc, og, out);
     } else {
-        temporal_tiles<true><<<(unsigned)tiles, 256, 0, st>>>(rgb, normal, depth, nullptr, nullptr, w, h, tiles_x, k, oc,
-                                                             og, out);
+        temporal_tiles<true><<<tiles, 256, 0, st>>>(rgb, normal, depth, nullptr, nullptr, w, h, tiles_x, k, oc, og, out);
     }
     return hipGetLastError();
 }

@@ -1,7 +1,7 @@
 // pt_temporal.hpp — temporal accumulation for a moving camera: the accumulated frame of the last
 // camera is reprojected through the new frame's first-hit distance into the new camera, rejected where the geometry
 // disagrees, and the new frame is blended in.  Built the way the denoiser is (pt_denoise.hpp): f64, no transcendental
-// function, one fixed order, so the GPU, the host build (tests/native/temporal.mk) and the numpy restatement
+// function, one fixed order, so the GPU, the host build (tests/native/Makefile) and the numpy restatement
 // (tests/temporalref.py) give the same bits.  A pass of its own: it reads three whole frames in the colour buffer's
 // layout (world == 1) and a history buffer, knows nothing of scenes or renderers, and the render kernels do not know
 // about it.

@@ -16,9 +16,7 @@
 
 #include <cmath>
 
-#ifndef PT_HD
-#define PT_HD __host__ __device__ __forceinline__
-#endif
+#include "pt_dims.hpp"
 
 namespace pt {
 namespace torus {

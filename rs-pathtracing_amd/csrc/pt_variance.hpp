@@ -3,7 +3,7 @@
 // between them; differencing those sums window by window gives K batch sums, and from them the variance of each
 // element's mean (the method of batch means).  No render kernel changes: this is a pass of its own, run on d_out
 // right after each window, in f64 with one fixed order of operations, so the GPU, the host build
-// (tests/native/variance.mk) and the numpy restatement (tests/varianceref.py) give the same bits.
+// (tests/native/Makefile) and the numpy restatement (tests/varianceref.py) give the same bits.
 //
 // An element is one double of d_out (a channel of a pixel; d_out's layout, the shard layout included).  Window k of
 // K covers samples [e_{k-1}, e_k), e_k = (uint64)k * N / K, n_k = e_k - e_{k-1}.  Per element, with the two doubles
@@ -24,9 +24,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#ifndef PT_HD
-#define PT_HD __host__ __device__ __forceinline__
-#endif
+#include "pt_dims.hpp"
 
 namespace pt {
 

@@ -66,7 +66,7 @@ extern "C" size_t ad_window(uint32_t w, uint32_t h, uint32_t rank, uint32_t worl
                             uint32_t k, uint32_t window, uint32_t min_samples, uint32_t max_samples, double threshold,
                             double luminance_floor, double *work, double *out, double *variance,
                             uint32_t *tile_samples, double *tile_error) {
-    const dev::AdaptiveGeom g{w, h, rank, world, (w + TILE - 1) / TILE, world > 1 ? 1u : 0u};
+    const dev::AdaptiveGeom g{w, h, rank, world, tiles_across(w), world > 1 ? 1u : 0u};
     const dev::AdaptiveConsts c = adaptive_consts(k, window, min_samples, max_samples, threshold, luminance_floor);
     if (k == 1) window_on_host<true>(g, ntiles, count, c, work, out, variance, tile_samples, tile_error);
     else window_on_host<false>(g, ntiles, count, c, work, out, variance, tile_samples, tile_error);

@@ -24,7 +24,7 @@ PLANS = [(1, 2), (3, 7), (8, 20), (8, 64)]  # (window, cap)
 
 @pytest.fixture(scope="module")
 def A():
-    subprocess.run(["make", "-s", "-C", str(NATIVE), "-f", "adaptive.mk"], check=True)
+    subprocess.run(["make", "-s", "-C", str(NATIVE), "_build/libadaptive.so"], check=True)
     L = C.CDLL(native_lib("libadaptive.so"))
     L.ad_window.restype = C.c_size_t
     L.ad_window.argtypes = ([C.c_uint32] * 5 + [C.c_size_t] + [C.c_uint32] * 4 +

@@ -1,5 +1,5 @@
 """The guide-plane pass on the CPU: dev::aov_pixel (rs-pathtracing_amd/csrc/pt_aov.hpp), the function the
-aov_tiles kernel runs per lane, compiled for the host by tests/native/aov.mk and run over every pixel, against the
+aov_tiles kernel runs per lane, compiled for the host by tests/native/Makefile and run over every pixel, against the
 planes tests/aovref.py computes from the oracle's pieces.  Bit for bit, except the textured scene (host libm on
 both sides here, but the project's frame tolerance is what the planes promise).  tests/test_gpu_aov.py repeats the
 comparison with the same code compiled for gfx950."""
@@ -18,7 +18,7 @@ NATIVE = Path(__file__).resolve().parent / "native"
 
 @pytest.fixture(scope="module")
 def A():
-    subprocess.run(["make", "-s", "-C", str(NATIVE), "-f", "aov.mk"], check=True)
+    subprocess.run(["make", "-s", "-C", str(NATIVE), "_build/libaov.so"], check=True)
     L = C.CDLL(native_lib("libaov.so"))
     d = C.POINTER(C.c_double)
     L.a_scene_new.restype = C.c_void_p

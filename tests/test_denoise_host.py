@@ -1,5 +1,5 @@
 """The guided denoiser on the CPU: the per-pixel functions of rs-pathtracing_amd/csrc/pt_denoise.hpp (the ones the
-denoise_records and denoise_tiles kernels run per lane), compiled for the host by tests/native/denoise.mk and run
+denoise_records and denoise_tiles kernels run per lane), compiled for the host by tests/native/Makefile and run
 over every pixel, against the numpy restatement tests/denoiseref.py, bit for bit; the identities that need no
 reference; the filter's quality against converged oracle frames; and pt_denoise's argument checks, which return
 before any HIP call.  tests/test_gpu_denoise.py repeats the comparison with the same code compiled for gfx950."""
@@ -21,7 +21,7 @@ INF = float("inf")
 
 @pytest.fixture(scope="module")
 def D():
-    subprocess.run(["make", "-s", "-C", str(NATIVE), "-f", "denoise.mk"], check=True)
+    subprocess.run(["make", "-s", "-C", str(NATIVE), "_build/libdenoise.so"], check=True)
     L = C.CDLL(native_lib("libdenoise.so"))
     d = C.POINTER(C.c_double)
     L.dn_denoise.restype = C.c_size_t
@@ -226,37 +226,107 @@ BAD = {
 }
 
 
-@pytest.mark.parametrize("case", list(BAD))
-def test_argument_errors(pt, case):
+# two bad arguments at once: the order of the checks decides which message wins
+BAD.update({
+    "null_rgb_and_unknown_flag": dict(rgb=None, flags=2),
+    "unknown_flag_and_zero_width": dict(flags=2, w=0),
+    "null_albedo_and_zero_height": dict(albedo=None, h=0),
+    "zero_width_and_no_iterations": dict(w=0, iterations=0),
+    "nine_iterations_and_sigma_normal_zero": dict(iterations=9, sn=0.0),
+    "sigma_depth_nan_and_sigma_colour_negative": dict(sd=NAN, sc=-1.0),
+    "sigma_colour_nan_and_too_large": dict(sc=NAN, w=1 << 20, h=1 << 20),
+})
+
+
+# pt_last_error() of each case, recorded from the build before the checks were given one spelling each
+MESSAGES = {'null_rgb': b'null argument',
+ 'null_normal': b'null argument',
+ 'null_depth': b'null argument',
+ 'null_albedo_with_demodulation': b'PT_DENOISE_DEMODULATE needs the albedo plane',
+ 'null_out': b'null argument',
+ 'zero_width': b'width and height must be > 0',
+ 'zero_height': b'width and height must be > 0',
+ 'no_iterations': b'iterations must be 1..8',
+ 'nine_iterations': b'iterations must be 1..8',
+ 'unknown_flag': b'unknown denoise flag',
+ 'unknown_flag_alone': b'unknown denoise flag',
+ 'sigma_normal_zero': b'sigma_normal and sigma_depth must be > 0',
+ 'sigma_normal_negative': b'sigma_normal and sigma_depth must be > 0',
+ 'sigma_normal_nan': b'sigma_normal and sigma_depth must be > 0',
+ 'sigma_depth_zero': b'sigma_normal and sigma_depth must be > 0',
+ 'sigma_depth_nan': b'sigma_normal and sigma_depth must be > 0',
+ 'sigma_colour_negative': b'sigma_colour must be >= 0',
+ 'sigma_colour_nan': b'sigma_colour must be >= 0',
+ 'null_rgb_and_unknown_flag': b'null argument',
+ 'unknown_flag_and_zero_width': b'unknown denoise flag',
+ 'null_albedo_and_zero_height': b'PT_DENOISE_DEMODULATE needs the albedo plane',
+ 'zero_width_and_no_iterations': b'width and height must be > 0',
+ 'nine_iterations_and_sigma_normal_zero': b'iterations must be 1..8',
+ 'sigma_depth_nan_and_sigma_colour_negative': b'sigma_normal and sigma_depth must be > 0',
+ 'sigma_colour_nan_and_too_large': b'sigma_colour must be >= 0'}
+MESSAGES_DEVICE = {'null_work': b'null argument',
+ 'misaligned_work': b'the workspace must be 16-byte aligned',
+ 'nine_iterations': b'iterations must be 1..8',
+ 'sigma_normal_nan': b'sigma_normal and sigma_depth must be > 0',
+ 'null_work_and_nine_iterations': b'iterations must be 1..8',
+ 'misaligned_work_and_null_out': b'null argument',
+ 'null_work_and_zero_width': b'width and height must be > 0'}
+
+
+def host_refusal(pt, bad):
+    """pt_denoise with the arguments of `bad` replaced: (status, message, the out buffer)."""
     w, h = 8, 4
     d = C.POINTER(C.c_double)
     a = dict(rgb=np.ones((w * h, 3)), albedo=np.ones((w * h, 3)), normal=np.zeros((w * h, 3)),
              depth=np.ones((w * h, 3)), out=np.full((w * h, 3), -7.25), w=w, h=h, iterations=5, sn=0.5, sd=0.1, sc=0.0,
              flags=1)
     out = a["out"]
-    a.update(BAD[case])
+    a.update(bad)
     ptr = {k: None if a[k] is None else a[k].ctypes.data_as(d) for k in ("rgb", "albedo", "normal", "depth", "out")}
     rc = pt.lib().pt_denoise(-1, ptr["rgb"], ptr["albedo"], ptr["normal"], ptr["depth"], a["w"], a["h"],
                              a["iterations"], a["sn"], a["sd"], a["sc"], a["flags"], ptr["out"])
+    return rc, pt.lib().pt_last_error(), out
+
+
+@pytest.mark.parametrize("case", list(BAD))
+def test_argument_errors(pt, case):
+    rc, message, out = host_refusal(pt, BAD[case])
     assert rc == pt.PT_ERR_INVALID, (case, rc)
-    assert pt.lib().pt_last_error()
+    assert message == MESSAGES[case]  # the text, as recorded before the checks were given one spelling each
     assert np.all(out == -7.25)  # a refused call writes nothing
 
 
-def test_device_form_argument_errors(pt):
-    """The device form's checks come before its first HIP call too: the shared ones, a null and a misaligned
-    workspace.  (The pointers are never dereferenced on the host.)"""
+def device_refusal(pt, bad):
+    """pt_denoise_device likewise; the pointers are never dereferenced on the host.  (status, message, the buffer)"""
     w, h = 8, 4
     buf = np.zeros(w * h * 3 + w * h * 12 + 2)
     base = buf.ctypes.data
-    work = (base + w * h * 24 + 15) & ~15
+    a = dict(work=(base + w * h * 24 + 15) & ~15, iterations=5, sn=0.5, w=w, out=base)
+    a.update(bad)
+    if a["work"] == "misaligned":
+        a["work"] = ((base + w * h * 24 + 15) & ~15) + 8
     L = pt.lib()
+    rc = L.pt_denoise_device(-1, base, base, base, base, a["w"], h, a["iterations"], a["sn"], 0.1, 0.0, 1, a["out"],
+                             a["work"], None)
+    return rc, L.pt_last_error(), buf
 
-    def call(work_ptr, iterations=5, sn=0.5):
-        return L.pt_denoise_device(-1, base, base, base, base, w, h, iterations, sn, 0.1, 0.0, 1, base, work_ptr, None)
 
-    assert call(None) == pt.PT_ERR_INVALID
-    assert call(work + 8) == pt.PT_ERR_INVALID and b"aligned" in L.pt_last_error()
-    assert call(work, iterations=9) == pt.PT_ERR_INVALID
-    assert call(work, sn=NAN) == pt.PT_ERR_INVALID
-    assert np.all(buf == 0.0)
+BAD_DEVICE = {
+    "null_work": dict(work=None),
+    "misaligned_work": dict(work="misaligned"),
+    "nine_iterations": dict(iterations=9),
+    "sigma_normal_nan": dict(sn=NAN),
+    "null_work_and_nine_iterations": dict(work=None, iterations=9),  # the shared checks come first
+    "misaligned_work_and_null_out": dict(work="misaligned", out=None),
+    "null_work_and_zero_width": dict(work=None, w=0),
+}
+
+
+def test_device_form_argument_errors(pt):
+    """The device form's checks come before its first HIP call too: the shared ones, then a null and a misaligned
+    workspace."""
+    for case, bad in BAD_DEVICE.items():
+        rc, message, buf = device_refusal(pt, bad)
+        assert rc == pt.PT_ERR_INVALID, (case, rc)
+        assert message == MESSAGES_DEVICE[case], case
+        assert np.all(buf == 0.0)

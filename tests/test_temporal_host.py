@@ -1,5 +1,5 @@
 """Temporal accumulation on the CPU: dev::temporal_pixel of rs-pathtracing_amd/csrc/pt_temporal.hpp (the function the
-temporal_tiles kernel runs per lane), compiled for the host by tests/native/temporal.mk and run over every pixel,
+temporal_tiles kernel runs per lane), compiled for the host by tests/native/Makefile and run over every pixel,
 against the numpy restatement tests/temporalref.py, bit for bit; the properties that need no reference; the relations
 the accumulated frame must keep against a converged oracle frame; and pt_temporal's argument checks, which return
 before any HIP call.  tests/test_gpu_temporal.py repeats the comparison with the same code compiled for gfx950."""
@@ -26,7 +26,7 @@ W, H = 40, 24
 
 @pytest.fixture(scope="module")
 def D():
-    subprocess.run(["make", "-s", "-C", str(NATIVE), "-f", "temporal.mk"], check=True)
+    subprocess.run(["make", "-s", "-C", str(NATIVE), "_build/libtemporal.so"], check=True)
     L = C.CDLL(native_lib("libtemporal.so"))
     d = C.POINTER(C.c_double)
     L.tp_temporal.restype = C.c_size_t
@@ -332,8 +332,59 @@ BAD = {
 }
 
 
-@pytest.mark.parametrize("case", list(BAD))
-def test_argument_errors(pt, case):
+# two bad arguments at once: the order of the checks decides which message wins
+BAD.update({
+    "null_rgb_and_zero_width": dict(rgb=None, w=0),
+    "zero_height_and_max_count_zero": dict(h=0, max_count=0),
+    "max_count_zero_and_sigma_normal_zero": dict(max_count=0, sn=0.0),
+    "sigma_depth_nan_and_history_without_camera": dict(sd=NAN, prev=None),
+    "camera_without_history_and_too_many_tiles": dict(hin=None, w=1 << 20, h=1 << 20),
+})
+
+
+# pt_last_error() of each case, recorded from the build before the checks were given one spelling each
+MESSAGES = {'null_rgb': b'null argument',
+ 'null_normal': b'null argument',
+ 'null_depth': b'null argument',
+ 'null_camera': b'null argument',
+ 'null_history_out': b'null argument',
+ 'null_out': b'null argument',
+ 'zero_width': b'width and height must be > 0',
+ 'zero_height': b'width and height must be > 0',
+ 'max_count_zero': b'max_count must be > 0',
+ 'sigma_normal_zero': b'sigma_normal and sigma_depth must be > 0',
+ 'sigma_normal_negative': b'sigma_normal and sigma_depth must be > 0',
+ 'sigma_normal_nan': b'sigma_normal and sigma_depth must be > 0',
+ 'sigma_depth_zero': b'sigma_normal and sigma_depth must be > 0',
+ 'sigma_depth_nan': b'sigma_normal and sigma_depth must be > 0',
+ 'history_without_camera': b'prev_camera and history_in are given together, or neither (the first frame)',
+ 'camera_without_history': b'prev_camera and history_in are given together, or neither (the first frame)',
+ 'histories_overlap': b'history_in and history_out overlap',
+ 'histories_equal': b'history_in and history_out overlap',
+ 'too_many_tiles': b'the frame is too large to accumulate in one call',
+ 'history_does_not_fit': b'the frame is too large to accumulate in one call',
+ 'null_rgb_and_zero_width': b'null argument',
+ 'zero_height_and_max_count_zero': b'width and height must be > 0',
+ 'max_count_zero_and_sigma_normal_zero': b'max_count must be > 0',
+ 'sigma_depth_nan_and_history_without_camera': b'sigma_normal and sigma_depth must be > 0',
+ 'camera_without_history_and_too_many_tiles': b'prev_camera and history_in are given together, or neither (the first'
+                                              b' frame)'}
+MESSAGES_DEVICE = {'misaligned_out_history': b'the histories must be 16-byte aligned',
+ 'misaligned_in_history': b'the histories must be 16-byte aligned',
+ 'first_frame_misaligned': b'the histories must be 16-byte aligned',
+ 'overlap': b'history_in and history_out overlap',
+ 'null_out_history': b'null argument',
+ 'null_in_history': b'prev_camera and history_in are given together, or neither (the first frame)',
+ 'history_without_camera': b'prev_camera and history_in are given together, or neither (the first frame)',
+ 'max_count_zero': b'max_count must be > 0',
+ 'sigma_normal_nan': b'sigma_normal and sigma_depth must be > 0',
+ 'misaligned_and_max_count_zero': b'max_count must be > 0',
+ 'misaligned_and_overlap': b'history_in and history_out overlap',
+ 'null_out_history_and_sigma_normal_nan': b'null argument'}
+
+
+def host_refusal(pt, bad):
+    """pt_temporal with the arguments of `bad` replaced: (status, message, the out buffer, the histories)."""
     w, h = 8, 4
     d = C.POINTER(C.c_double)
     cam = pt.Camera.new((0, 0, 0), (0, 0, 1), (0, 1, 0), 1.0, 0.7)
@@ -342,42 +393,72 @@ def test_argument_errors(pt, case):
              out=np.full((w * h, 3), SENTINEL), hin=hist[:w * h * 8], hout=hist[w * h * 8:w * h * 16], camera=cam,
              prev=cam, w=w, h=h, max_count=32, sn=0.5, sd=0.1)
     out = a["out"]
-    a.update(BAD[case])
+    a.update(bad)
     if "overlap" in a:
         a["hout"] = hist[a["overlap"]:a["overlap"] + w * h * 8]
     ptr = {k: None if a[k] is None else a[k].ctypes.data_as(d) for k in ("rgb", "normal", "depth", "out", "hin", "hout")}
     cams = {k: None if a[k] is None else C.byref(a[k]._c) for k in ("camera", "prev")}
     rc = pt.lib().pt_temporal(-1, ptr["rgb"], ptr["normal"], ptr["depth"], cams["camera"], cams["prev"], a["w"],
                               a["h"], ptr["hin"], ptr["hout"], a["max_count"], a["sn"], a["sd"], ptr["out"])
+    return rc, pt.lib().pt_last_error(), out, hist
+
+
+@pytest.mark.parametrize("case", list(BAD))
+def test_argument_errors(pt, case):
+    rc, message, out, hist = host_refusal(pt, BAD[case])
     assert rc == pt.PT_ERR_INVALID, (case, rc)
-    assert pt.lib().pt_last_error()
+    assert message == MESSAGES[case]  # the text, as recorded before the checks were given one spelling each
     assert np.all(out == SENTINEL) and np.all(hist == SENTINEL)  # a refused call writes nothing
 
 
-def test_device_form_argument_errors(pt):
-    """The device form's checks come before its first HIP call too: the shared ones and a misaligned history.  (The
-    pointers are never dereferenced on the host.)"""
+# the device form: (hin, hout) as offsets in bytes from two aligned, well separated histories, None for a null pointer
+BAD_DEVICE = {
+    "misaligned_out_history": dict(hout=8),
+    "misaligned_in_history": dict(hin=8),
+    "first_frame_misaligned": dict(hin=None, hout=8, prev=None),
+    "overlap": dict(hout="hin+16"),
+    "null_out_history": dict(hout=None),
+    "null_in_history": dict(hin=None),
+    "history_without_camera": dict(prev=None),
+    "max_count_zero": dict(max_count=0),
+    "sigma_normal_nan": dict(sn=NAN),
+    "misaligned_and_max_count_zero": dict(hout=8, max_count=0),  # two at once: the shared checks come first
+    "misaligned_and_overlap": dict(hin=8, hout="hin+16"),
+    "null_out_history_and_sigma_normal_nan": dict(hout=None, sn=NAN),
+}
+
+
+def device_refusal(pt, bad):
+    """pt_temporal_device likewise; the pointers are never dereferenced on the host.  (status, message, the buffer)"""
     w, h = 8, 4
     buf = np.zeros(w * h * 3 + w * h * 16 + 12)
     base = buf.ctypes.data
     hin = (base + w * h * 24 + 15) & ~15
     hout = hin + w * h * 64 + 32  # a gap, so that a pointer moved by 8 bytes does not overlap
     cam = pt.Camera.new((0, 0, 0), (0, 0, 1), (0, 1, 0), 1.0, 0.7)
+    a = dict(hin=0, hout=0, prev=cam, max_count=32, sn=0.5)
+    a.update(bad)
+    p_in = None if a["hin"] is None else hin + a["hin"]
+    p_out = None if a["hout"] is None else (p_in + 16 if a["hout"] == "hin+16" else hout + a["hout"])
     L = pt.lib()
+    rc = L.pt_temporal_device(-1, base, base, base, C.byref(cam._c), None if a["prev"] is None else C.byref(a["prev"]._c),
+                              w, h, p_in, p_out, a["max_count"], a["sn"], 0.1, base, None)
+    return rc, L.pt_last_error(), buf
 
-    def call(hin, hout, prev=cam, max_count=32, sn=0.5):
-        return L.pt_temporal_device(-1, base, base, base, C.byref(cam._c), None if prev is None else C.byref(prev._c),
-                                    w, h, hin, hout, max_count, sn, 0.1, base, None)
 
-    assert call(hin, hout + 8) == pt.PT_ERR_INVALID and b"aligned" in L.pt_last_error()
-    assert call(hin + 8, hout) == pt.PT_ERR_INVALID and b"aligned" in L.pt_last_error()
-    assert call(None, hout + 8, prev=None) == pt.PT_ERR_INVALID and b"aligned" in L.pt_last_error()
-    assert call(hin, hin + 16) == pt.PT_ERR_INVALID and b"overlap" in L.pt_last_error()
-    assert call(hin, None) == pt.PT_ERR_INVALID
-    assert call(None, hout) == pt.PT_ERR_INVALID
-    assert call(hin, hout, prev=None) == pt.PT_ERR_INVALID
-    assert call(hin, hout, max_count=0) == pt.PT_ERR_INVALID
-    assert call(hin, hout, sn=NAN) == pt.PT_ERR_INVALID
+def test_device_form_argument_errors(pt):
+    """The device form's checks come before its first HIP call too: the shared ones and a misaligned history."""
+    for case, bad in BAD_DEVICE.items():
+        rc, message, buf = device_refusal(pt, bad)
+        assert rc == pt.PT_ERR_INVALID, (case, rc)
+        assert message == MESSAGES_DEVICE[case], case
+        assert np.all(buf == 0.0)
+    w, h = 8, 4
+    buf = np.zeros(w * h * 3 + w * h * 16 + 12)
+    base = buf.ctypes.data
+    hin = (base + w * h * 24 + 15) & ~15
+    hout = hin + w * h * 64 + 32
+    cam = pt.Camera.new((0, 0, 0), (0, 0, 1), (0, 1, 0), 1.0, 0.7)
     with pytest.raises(pt.PtError) as e:
         pt.temporal_device(base, base, base, cam, cam, w, h, hin, hout + 8, base)
     assert e.value.code == pt.PT_ERR_INVALID

@@ -22,7 +22,7 @@ NAMES = ("pt_render_device_tiles", "pt_render_adaptive_list_device", "pt_render_
 
 @pytest.fixture(scope="module")
 def T():
-    subprocess.run(["make", "-s", "-C", str(NATIVE), "-f", "tile_list.mk"], check=True)
+    subprocess.run(["make", "-s", "-C", str(NATIVE), "_build/libtilelist.so"], check=True)
     L = C.CDLL(native_lib("libtilelist.so"))
     L.tl_ok.restype = C.c_int
     L.tl_ok.argtypes = [u32p, C.c_size_t, C.c_uint32]

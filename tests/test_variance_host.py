@@ -1,7 +1,7 @@
 """The variance estimate and the denoiser's variance term on the CPU: the per-element function of
 rs-pathtracing_amd/csrc/pt_variance.hpp and the per-pixel functions of pt_denoise.hpp (the ones the variance_window,
 denoise_records_variance and denoise_tiles_variance kernels run per lane), compiled for the host by
-tests/native/variance.mk, against the numpy restatement tests/varianceref.py, bit for bit; the identity with the plain
+tests/native/Makefile, against the numpy restatement tests/varianceref.py, bit for bit; the identity with the plain
 denoiser; the filter's quality and the estimate's size against converged oracle frames; and the argument checks of the
 new exports, which return before any HIP call.  tests/test_gpu_variance.py repeats the comparisons with the same code
 compiled for gfx950."""
@@ -27,7 +27,7 @@ d = C.POINTER(C.c_double)
 
 @pytest.fixture(scope="module")
 def V():
-    subprocess.run(["make", "-s", "-C", str(NATIVE), "-f", "variance.mk"], check=True)
+    subprocess.run(["make", "-s", "-C", str(NATIVE), "_build/libvariance.so"], check=True)
     L = C.CDLL(native_lib("libvariance.so"))
     L.vr_window.restype = C.c_size_t
     L.vr_window.argtypes = [d, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, d, d]
@@ -306,51 +306,150 @@ BAD_DENOISE = {
 }
 
 
-@pytest.mark.parametrize("case", list(BAD_DENOISE))
-def test_denoise_variance_argument_errors(pt, case):
+# two bad arguments at once: the order of the checks decides which message wins
+BAD_DENOISE.update({
+    "null_variance_and_sigma_variance_zero": dict(variance=None, sv=0.0),
+    "sigma_variance_nan_and_null_rgb": dict(sv=NAN, rgb=None),
+    "null_out_and_unknown_flag": dict(out=None, flags=2),
+    "unknown_flag_and_zero_width": dict(flags=2, w=0),
+    "zero_height_and_nine_iterations": dict(h=0, iterations=9),
+    "no_iterations_and_sigma_depth_nan": dict(iterations=0, sd=NAN),
+    "sigma_normal_zero_and_too_large": dict(sn=0.0, w=1 << 20, h=1 << 20),
+})
+
+
+# pt_last_error() of each case, recorded from the build before the checks were given one spelling each
+MESSAGES_DENOISE = {'null_rgb': b'null argument',
+ 'null_normal': b'null argument',
+ 'null_depth': b'null argument',
+ 'null_variance': b'null argument',
+ 'null_albedo_with_demodulation': b'PT_DENOISE_DEMODULATE needs the albedo plane',
+ 'null_out': b'null argument',
+ 'zero_width': b'width and height must be > 0',
+ 'zero_height': b'width and height must be > 0',
+ 'no_iterations': b'iterations must be 1..8',
+ 'nine_iterations': b'iterations must be 1..8',
+ 'unknown_flag': b'unknown denoise flag',
+ 'sigma_normal_zero': b'sigma_normal and sigma_depth must be > 0',
+ 'sigma_depth_nan': b'sigma_normal and sigma_depth must be > 0',
+ 'sigma_variance_zero': b'sigma_variance must be > 0',
+ 'sigma_variance_negative': b'sigma_variance must be > 0',
+ 'sigma_variance_nan': b'sigma_variance must be > 0',
+ 'null_variance_and_sigma_variance_zero': b'null argument',
+ 'sigma_variance_nan_and_null_rgb': b'sigma_variance must be > 0',
+ 'null_out_and_unknown_flag': b'null argument',
+ 'unknown_flag_and_zero_width': b'unknown denoise flag',
+ 'zero_height_and_nine_iterations': b'width and height must be > 0',
+ 'no_iterations_and_sigma_depth_nan': b'iterations must be 1..8',
+ 'sigma_normal_zero_and_too_large': b'sigma_normal and sigma_depth must be > 0'}
+MESSAGES_DENOISE_DEVICE = {'null_work': b'null argument',
+ 'misaligned_work': b'the workspace must be 16-byte aligned',
+ 'null_variance': b'null argument',
+ 'null_out': b'null argument',
+ 'nine_iterations': b'iterations must be 1..8',
+ 'sigma_variance_zero': b'sigma_variance must be > 0',
+ 'sigma_variance_negative': b'sigma_variance must be > 0',
+ 'sigma_variance_nan': b'sigma_variance must be > 0',
+ 'null_variance_and_null_work': b'null argument',
+ 'sigma_variance_zero_and_null_out': b'sigma_variance must be > 0',
+ 'misaligned_work_and_nine_iterations': b'iterations must be 1..8'}
+MESSAGES_WINDOW = {'null_out': b'null argument',
+ 'null_work': b'null argument',
+ 'null_variance': b'null argument',
+ 'no_count': b'count must be > 0 and fit one launch',
+ 'n_k_zero': b'n_k must be 1..samples_number',
+ 'n_k_above': b'n_k must be 1..samples_number',
+ 'window_zero': b'window must be 1..windows',
+ 'window_above': b'window must be 1..windows',
+ 'one_window': b'windows must be 2..samples_number',
+ 'no_windows': b'windows must be 2..samples_number',
+ 'windows_above': b'windows must be 2..samples_number',
+ 'null_work_and_no_count': b'null argument',
+ 'no_count_and_one_window': b'count must be > 0 and fit one launch',
+ 'one_window_and_window_zero': b'windows must be 2..samples_number',
+ 'window_above_and_n_k_zero': b'window must be 1..windows'}
+
+
+def denoise_refusal(pt, bad):
+    """pt_denoise_variance with the arguments of `bad` replaced: (status, message, the out buffer)."""
     w, h = 8, 4
     a = dict(rgb=np.ones((w * h, 3)), albedo=np.ones((w * h, 3)), normal=np.zeros((w * h, 3)),
              depth=np.ones((w * h, 3)), variance=np.ones((w * h, 3)), out=np.full((w * h, 3), -7.25), w=w, h=h,
              iterations=5, sn=0.5, sd=0.1, sv=8.0, flags=1)
     out = a["out"]
-    a.update(BAD_DENOISE[case])
+    a.update(bad)
     ptr = {k: None if a[k] is None else a[k].ctypes.data_as(d)
            for k in ("rgb", "albedo", "normal", "depth", "variance", "out")}
     rc = pt.lib().pt_denoise_variance(-1, ptr["rgb"], ptr["albedo"], ptr["normal"], ptr["depth"], ptr["variance"],
                                       a["w"], a["h"], a["iterations"], a["sn"], a["sd"], a["sv"], a["flags"], ptr["out"])
+    return rc, pt.lib().pt_last_error(), out
+
+
+@pytest.mark.parametrize("case", list(BAD_DENOISE))
+def test_denoise_variance_argument_errors(pt, case):
+    rc, message, out = denoise_refusal(pt, BAD_DENOISE[case])
     assert rc == pt.PT_ERR_INVALID, (case, rc)
-    assert pt.lib().pt_last_error()
+    assert message == MESSAGES_DENOISE[case]  # the text, as recorded before the checks were given one spelling each
     assert np.all(out == -7.25)  # a refused call writes nothing
 
 
-def test_device_forms_argument_errors(pt):
-    """The device forms' checks come before their first HIP call: the pointers are never dereferenced on the host."""
+BAD_DENOISE_DEVICE = {
+    "null_work": dict(work=None),
+    "misaligned_work": dict(work="misaligned"),
+    "null_variance": dict(var=None),
+    "null_out": dict(out=None),
+    "nine_iterations": dict(iterations=9),
+    "sigma_variance_zero": dict(sv=0.0),
+    "sigma_variance_negative": dict(sv=-1.0),
+    "sigma_variance_nan": dict(sv=NAN),
+    "null_variance_and_null_work": dict(var=None, work=None),  # two at once: the shared checks come first
+    "sigma_variance_zero_and_null_out": dict(sv=0.0, out=None),
+    "misaligned_work_and_nine_iterations": dict(work="misaligned", iterations=9),
+}
+BAD_WINDOW = {
+    "null_out": dict(out=None), "null_work": dict(wk=None), "null_variance": dict(var=None), "no_count": dict(cnt=0),
+    "n_k_zero": dict(n_k=0), "n_k_above": dict(n_k=17), "window_zero": dict(window=0), "window_above": dict(window=9),
+    "one_window": dict(windows=1), "no_windows": dict(windows=0), "windows_above": dict(windows=17, window=17),
+    "null_work_and_no_count": dict(wk=None, cnt=0),  # two at once
+    "no_count_and_one_window": dict(cnt=0, windows=1),
+    "one_window_and_window_zero": dict(windows=1, window=0),
+    "window_above_and_n_k_zero": dict(window=9, n_k=0),
+}
+
+
+def device_refusal(pt, name, bad):
+    """pt_denoise_variance_device or pt_variance_window_device likewise; the pointers are never dereferenced on the
+    host.  (status, message, the buffer)"""
     w, h = 8, 4
     count = w * h * 3
     buf = np.zeros(count + w * h * 12 + 2)
     base = buf.ctypes.data
     work = (base + count * 8 + 15) & ~15
     L = pt.lib()
+    if name == "pt_denoise_variance_device":
+        a = dict(work=work, var=base, iterations=5, sv=8.0, out=base)
+        a.update(bad)
+        if a["work"] == "misaligned":
+            a["work"] = work + 8
+        rc = L.pt_denoise_variance_device(-1, base, base, base, base, a["var"], w, h, a["iterations"], 0.5, 0.1, a["sv"],
+                                          1, a["out"], a["work"], None)
+    else:
+        a = dict(out=base, cnt=count, n_k=2, n=16, window=1, windows=8, wk=work, var=base)
+        a.update(bad)
+        rc = L.pt_variance_window_device(-1, a["out"], a["cnt"], a["n_k"], a["n"], a["window"], a["windows"], a["wk"],
+                                         a["var"], None)
+    return rc, L.pt_last_error(), buf
 
-    def dn(work_ptr=work, var=base, iterations=5, sv=8.0, out=base):
-        return L.pt_denoise_variance_device(-1, base, base, base, base, var, w, h, iterations, 0.5, 0.1, sv, 1, out,
-                                            work_ptr, None)
 
-    assert dn(work_ptr=None) == pt.PT_ERR_INVALID
-    assert dn(work_ptr=work + 8) == pt.PT_ERR_INVALID and b"aligned" in L.pt_last_error()
-    assert dn(var=None) == pt.PT_ERR_INVALID and dn(out=None) == pt.PT_ERR_INVALID
-    assert dn(iterations=9) == pt.PT_ERR_INVALID
-    for sv in (0.0, -1.0, NAN):
-        assert dn(sv=sv) == pt.PT_ERR_INVALID and b"sigma_variance" in L.pt_last_error()
-
-    def win(out=base, cnt=count, n_k=2, n=16, window=1, windows=8, wk=work, var=base):
-        return L.pt_variance_window_device(-1, out, cnt, n_k, n, window, windows, wk, var, None)
-
-    for bad in (dict(out=None), dict(wk=None), dict(var=None), dict(cnt=0), dict(n_k=0), dict(n_k=17), dict(window=0),
-                dict(window=9), dict(windows=1), dict(windows=0), dict(windows=17, window=17)):
-        assert win(**bad) == pt.PT_ERR_INVALID, bad
-        assert L.pt_last_error()
-    assert np.all(buf == 0.0)
+def test_device_forms_argument_errors(pt):
+    """The device forms' checks come before their first HIP call."""
+    for name, cases, messages in (("pt_denoise_variance_device", BAD_DENOISE_DEVICE, MESSAGES_DENOISE_DEVICE),
+                                  ("pt_variance_window_device", BAD_WINDOW, MESSAGES_WINDOW)):
+        for case, bad in cases.items():
+            rc, message, buf = device_refusal(pt, name, bad)
+            assert rc == pt.PT_ERR_INVALID, (name, case, rc)
+            assert message == messages[case], (name, case)
+            assert np.all(buf == 0.0)
 
 
 def test_render_variance_argument_errors(pt, cornell_text):
