@@ -1144,7 +1144,9 @@ PT_HD V3 trace_pixel(const Scene &sc, const FrameParams &P, uint32_t x, uint32_t
                 const DShape &S = sc.shapes[i];
                 if (STATS) ct->c[C_TEST_MARCH]++;
                 V3 o = xf_point(S.inv, ray.o), d = xf_vector(S.inv, ray.d);
-                if (march::march_begin<FK>(shape_params(S), S.p[0], S.depth, o.x, o.y, o.z, d.x, d.y, d.z, &ms)) {
+                // (the march stops at the best hit so far: march::clip_to_best)
+                if (march::march_begin<FK>(shape_params(S), S.p[0], S.depth, o.x, o.y, o.z, d.x, d.y, d.z, &ms) &&
+                    march::clip_to_best(best, S.p[0], &ms.start, &ms.end)) {
                     mshape = i;
                     phase = PH_MARCH;
                     break;

@@ -662,6 +662,31 @@ PT_HD bool march_begin(const FParams &F, double step0, int passes, double ox, do
     return true;
 }
 
+// Clip a march's bound interval [*start, *end] to the caller's best hit so far: the march cannot use anything past
+// cap = best + 4 |step0|.  False: no job (the interval starts past the cap).  A best of +inf changes nothing.
+// Exact, for a caller that ends with the reference's final test `t < min_t || t > best` (ray_marching.rs:55-57):
+//  * march_iter tests `t > end || t < start` before every step and reads `end` nowhere else that decides a result
+//    (lim, the block sizes and the early-miss proof only choose how the same literal sequence is skipped through),
+//    so the clipped and the unclipped march are the same sequence of points until some t > cap;
+//  * from there the clipped march misses, and the unclipped one misses too or crosses at a coarse point t_c > cap;
+//  * passes 1 to 3 step by -0.01, 0.0001 and -0.000001 of step0 and each ends at the first sign change, which the
+//    previous pass's last two points bracket: pass 1 turns within one coarse step below t_c, the later ones within
+//    their own step of that, so every later point lies above t_c - 1.0101 |step0| (plus a rounding of t per step);
+//  * so the unclipped march's final t > cap - 1.02 |step0| > best, and the caller's `t > best` discards it: a miss;
+//  * a crossing found at a point t <= cap is found by both, and the clipped march's later passes either stay at or
+//    below cap (the same points, the same t) or pass it (a miss, where the unclipped t is again > best);
+//  * an interval with start > cap can only give t >= start - 0.0101 |step0| > best.
+// The margin of 4 steps is far more than the argument needs, on purpose.
+#ifndef PT_MCLIP  // host-only capture hook (tests/march_clip), a no-op in the product
+#define PT_MCLIP(best, step0, start, end) ((void)0)
+#endif
+PT_HD bool clip_to_best(double best, double step0, double *start, double *end) {
+    PT_MCLIP(best, step0, *start, *end);
+    const double cap = best + 4.0 * fabs(step0);
+    *end = fmin(*end, cap);
+    return !(*start > cap);
+}
+
 // One round of a proven block's exact advance: one binade segment for each
 // of t, px, py, pz that still has steps to go; when all are done the block's
 // end point is exact and f is evaluated there.

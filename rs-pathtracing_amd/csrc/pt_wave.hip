@@ -418,6 +418,9 @@ __global__ __launch_bounds__(256, WAVES) void wf_bounce(const WfArgs *__restrict
                 jo_d = dev::xf_vector(S.inv, ray.d);
                 need_march = march::shape_bound_k<FK>(dev::shape_params(S), jo_o.x, jo_o.y, jo_o.z, jo_d.x, jo_d.y,
                                                       jo_d.z, &jo_st, &jo_en);
+                // nothing the march finds past the best hit can be used (march::clip_to_best): the job's chord
+                // ends there, and a chord that starts behind it is no job
+                need_march = need_march && march::clip_to_best(best, S.p[0], &jo_st, &jo_en);
             }
             PT_BSTAMP(5)
             if (!need_march && dev::shade_decided(who, depth)) {
@@ -887,7 +890,8 @@ __global__ __launch_bounds__(256, WF_MARCH_WAVES) void wf_march(const WfArgs *__
                     const DShape &S = sc.shapes[s];
                     const V3 o = dev::xf_point(S.inv, cur.ray.o), d = dev::xf_vector(S.inv, cur.ray.d);
                     if (march::march_begin<FK>(dev::shape_params(S), S.p[0], S.depth, o.x, o.y, o.z, d.x, d.y,
-                                               d.z, &ms)) {
+                                               d.z, &ms) &&
+                        march::clip_to_best(cur.best, S.p[0], &ms.start, &ms.end)) {
                         mshape = s;
                         marching = true;
                         break;
