@@ -191,7 +191,10 @@ int pt_renderer_peer_access(const pt_renderer *r, int *pairs, int *enabled);
  * and "ran_mega", "ran_bounce", "ran_walk", "ran_march" (-1: the frame
  * launched none of that kernel; else the kernel build's template arguments
  * as sum((argument + 2) << (6 * position)), in the order of pt_builds.hpp's
- * lists of builds). */
+ * lists of builds).  "first_cull_bits" (read-only too) is
+ * the number of set bits over the first bounce launch's cull table of that
+ * frame (one mask per 8x8 pixel block), read once the frame
+ * is done; -1: the frame used no table. */
 int pt_renderer_set_option(pt_renderer *r, const char *name, int64_t value);
 int pt_renderer_get_option(const pt_renderer *r, const char *name, int64_t *value);
 const char *pt_option_name(int index);

@@ -425,6 +425,7 @@ int commit_accel(GpuShare &g, StagedAccel &a) {
     HIP_TRY(hipDeviceSynchronize());
     StagedAccel old = g.ds.view;
     view_set_accel(g.ds.view, a);
+    g.ds.accel_gen++;  // (what the workspace derived from the old structure is stale: its first-bounce cull table)
     a = StagedAccel{};
     free_staged(g.device, old);
     return PT_OK;
@@ -785,6 +786,11 @@ int pt_renderer_get_option(const pt_renderer *r, const char *name, int64_t *valu
     }
     // read-only too: what device 0's last launch_render call launched (builds::Ran; set_option knows no such name)
     if (ran_get(r->gpus[0].ws.ran, name, value)) return PT_OK;
+    if (!std::strcmp(name, "first_cull_bits")) {  // read-only: the first-bounce cull table of device 0's last frame
+        HIP_TRY(hipSetDevice(r->gpus[0].device));
+        HIP_TRY(first_cull_bits(r->gpus[0].ws, value));
+        return PT_OK;
+    }
     if (!tuning_get(r->gpus[0].ws.tune, name, value)) return fail(PT_ERR_INVALID, std::string("unknown option: ") + name);
     return PT_OK;
 }

@@ -11,6 +11,7 @@
 
 #include <cstdint>
 
+#include "pt_cull.hpp"
 #include "pt_lprof.hpp"
 #include "pt_march.hpp"
 #include "pt_tiles.hpp"
@@ -388,9 +389,16 @@ PT_HD void bvh_leaf_test(const Scene &sc, const Ray &r, bool axis_ok, int first,
 // instead of 32: t = fma(q, gs / d, (g0 - o) / d -/+ e') per plane, the same culling with the grid folded into
 // the per-ray offsets and a wider margin (below).
 // PART: bit 0 the uniform list, bit 1 the BVH.
-template <bool STATS = false, bool EXT = false, bool FMA_SLAB = false, bool QN = false, int PART = 3>
+// CULL (the first bounce launch, whose waves are one pixel block of camera rays each): cull_mask is the block's mask
+// (cull::first_cull_mask, pt_cull.hpp), the same in every lane; list position k < 32 is skipped, before its shape is
+// loaded, when bit k is clear.  Such an entry has no hit for any ray of the wave, so (best, who) are what the full
+// scan gives.  A rectangle group's products are then formed at the first member visited, from that member's own
+// m[0..10] (the group's members have the same nine linear entries bit for bit: group_rectangles), under a
+// wave-uniform "products valid" flag that every group head clears, culled or not.
+template <bool STATS = false, bool EXT = false, bool FMA_SLAB = false, bool QN = false, int PART = 3,
+          bool CULL = false>
 PT_HD void closest_nomarch(const Scene &sc, const Ray &r, V3 inv, double min_t, double *best_t, int *who_out,
-                           Ctr *ct = nullptr, bool any = false) {
+                           Ctr *ct = nullptr, bool any = false, uint64_t cull_mask = ~0ull) {
     double best = *best_t;
     int who = *who_out;
     // wave-uniform list (few JSON shapes): scalar loads of each shape
@@ -401,16 +409,22 @@ PT_HD void closest_nomarch(const Scene &sc, const Ray &r, V3 inv, double min_t, 
     // addition (of m[11], m[3], m[7]), g_dz, g_dx, g_dy the direction.  Each value is formed by shape_test's
     // operations in shape_test's order, so every t is the one shape_test gives (C2 +1.6 %).
     double g_pz = 0.0, g_dz = 1.0, g_ox = 0.0, g_oy = 0.0, g_dx = 0.0, g_dy = 0.0;
+    bool g_valid = false;  // (CULL) the products are those of the current group
     for (int k = 0; k < ((PART & 1) ? sc.nlin : 0); k++) {
         if (any && wave_all(who >= 0)) break;
         const int entry = uniform_index(uniform_load(&sc.lin[k]));
         const int i = entry & LIN_ID_MASK;
+        if (CULL) {
+            if (!(entry & LIN_GROUPED)) g_valid = false;
+            if (k < cull::LIST_BITS && !((cull_mask >> k) & 1ull)) continue;
+        }
         const DShape s = uniform_shape(&sc.shapes[i]);
         PT_LP(ULIST_SHAPE);
         if (s.type == RECTANGLE) {
             if (STATS) ct->c[C_TEST_RECT]++;
             const double *m = s.inv;
-            if (!(entry & LIN_GROUPED)) {
+            if (CULL ? !g_valid : !(entry & LIN_GROUPED)) {
+                g_valid = true;
                 g_pz = r.o.x * m[8] + r.o.y * m[9] + r.o.z * m[10];
                 g_dz = r.d.x * m[8] + r.d.y * m[9] + r.d.z * m[10];
                 g_ox = r.o.x * m[0] + r.o.y * m[1] + r.o.z * m[2];

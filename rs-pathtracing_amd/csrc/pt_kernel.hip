@@ -248,11 +248,12 @@ __global__ __launch_bounds__(256, 2) void render_tiles_timed(dev::Scene sc, Fram
     }
 
 hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P, double *out, hipStream_t st,
-                              WaveWorkspace *ws, const builds::Choice &ch, const uint32_t *tiles);
+                              WaveWorkspace *ws, const builds::Choice &ch, const uint32_t *tiles, uint64_t accel_gen);
 
 hipError_t launch_render(const DeviceScene &s, const FrameParams &P, double *out, hipStream_t st, WaveWorkspace &ws,
                          const uint32_t *tiles) {
     ws.ran = builds::Ran{};  // what this call launches: set below and in launch_render_wave, where a launch is made
+    ws.first_cull.used = false;  // (set where a frame is given the table)
     if (P.tile_count == 0) return hipSuccess;
     ws.refusal[0] = 0;
     builds::Inputs in{};
@@ -272,7 +273,7 @@ hipError_t launch_render(const DeviceScene &s, const FrameParams &P, double *out
     in.tune = ws.tune;
     const builds::Choice ch = builds::choose(in);
     if (ch.engine == builds::REFUSE) return hipErrorInvalidValue;
-    if (ch.engine == builds::WAVE) return launch_render_wave(s.view, P, out, st, &ws, ch, tiles);
+    if (ch.engine == builds::WAVE) return launch_render_wave(s.view, P, out, st, &ws, ch, tiles, s.accel_gen);
     if (tiles) return hipErrorInvalidValue;  // (never: a listed launch is a window)
     hipError_t e0 = timer_begin(ws.timer, st, K_MEGA);
     if (e0 != hipSuccess) return e0;

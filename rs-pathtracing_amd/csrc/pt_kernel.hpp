@@ -4,6 +4,7 @@
 
 #include "../../include/rs_pathtracing.h"
 #include "pt_builds.hpp"  // Tuning, tuning_set / tuning_get, the choice of kernel builds
+#include "pt_cull.hpp"
 #include "pt_types.hpp"
 
 namespace pt {
@@ -14,6 +15,9 @@ struct DeviceScene {
     dev::Scene view = {};
     int nshapes = 0;
     int fkind = 0;  // scene_builds(): 0: every marched shape is a Heart (or none) -> Heart-only kernel builds; -1: any
+    // counts the acceleration structures this device has been given (commit_accel): what was derived from one
+    // (WaveWorkspace::first_cull) is stale once it moves, even if a later structure's buffers reuse its addresses
+    uint64_t accel_gen = 0;
 };
 
 // Per-kernel launch timing (pt_kernel_timing): HIP events recorded on the
@@ -63,8 +67,24 @@ struct WaveWorkspace {
     char refusal[320] = {};
     // the engine and the kernel builds the last launch_render call launched (pt_renderer_get_option "ran_*")
     builds::Ran ran;
+    // The first bounce launch's cull table (pt_cull.hpp): one mask per 8x8 pixel block of the frame, filled on the
+    // frame's stream before its chunks fork (pt_wave.hip first_cull_table) and kept for the frames after it: it is
+    // remade only when the caster part of FrameParams, the frame's size or the device's acceleration data change.
+    struct FirstCull {
+        uint64_t *table = nullptr;
+        size_t cap = 0;      // masks the buffer holds
+        size_t blocks = 0;   // masks of the table in it
+        bool valid = false;  // the table is the one of (key, accel_gen, boxes)
+        cull::CasterKey key = {};
+        uint64_t accel_gen = 0;  // DeviceScene::accel_gen, and the buffer the boxes were read from
+        const void *boxes = nullptr;
+        bool used = false;  // the last launch_render call's frame read the table ("first_cull_bits")
+    } first_cull;
 };
 void wave_workspace_free(WaveWorkspace *ws);
+// The set bits over the cull table that the last launch_render call's frame read, once that frame is done; -1: it
+// read none (the megakernel, a SPLIT build's frame, a scene with nothing to cull).
+hipError_t first_cull_bits(const WaveWorkspace &ws, int64_t *bits);
 
 // Renders this rank's tiles of P into out with the engine and the kernel builds that builds::choose picks
 // (pt_builds.hpp).  An error with ws.refusal set is a refusal, not a HIP failure.

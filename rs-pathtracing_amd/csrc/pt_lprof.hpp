@@ -181,9 +181,18 @@ __device__ __forceinline__ void end_kernel() {
 #if defined(PT_LANE_PROF) && defined(__HIP_DEVICE_COMPILE__)
 #define PT_LP(k) pt::lprof::hit(pt::lprof::k)
 #define PT_LP_BEGIN() pt::lprof::begin_kernel()
-#define PT_LP_END() pt::lprof::end_kernel()
+// (with -DPT_LANE_PROF_IT=n as well, only the launches of bounce iteration n are counted: the others drop their
+// counts at the kernel's end)
+#ifdef PT_LANE_PROF_IT
+#define PT_LP_END(it)                                      \
+    do {                                                   \
+        if ((it) == PT_LANE_PROF_IT) pt::lprof::end_kernel(); \
+    } while (0)
+#else
+#define PT_LP_END(it) pt::lprof::end_kernel()
+#endif
 #else
 #define PT_LP(k) ((void)0)
 #define PT_LP_BEGIN() ((void)0)
-#define PT_LP_END() ((void)0)
+#define PT_LP_END(it) ((void)0)
 #endif

@@ -130,6 +130,9 @@ struct WfView {
     // a listed launch (launch_render's `tiles`): position tile0 + g of the launch stands for entry
     // tile_map[tile0 + g] of the rank's tile list; null: the position is the entry
     const uint32_t *tile_map;
+    // the frame's first-bounce cull table (pt_cull.hpp): one mask per 8x8 pixel block, block (bx, by) of the frame
+    // at [by * blocks_across(width) + bx]; null: no culling
+    const uint64_t *cull;
 };
 
 // What a launch of the wavefront kernels reads besides its iteration: the
@@ -341,10 +344,11 @@ __global__ __launch_bounds__(256, WAVES) void wf_bounce(const WfArgs *__restrict
         // pending hit of the path (non-first iterations: from the state)
         int who = -1;
         double best = 0.0;
+        uint32_t x = 0, y = 0;  // (FIRST) the slot's pixel
         if (live) {
             if (FIRST) {
                 id = i;
-                uint32_t x, y, sl, pl;
+                uint32_t sl, pl;
                 slot_pixel(P, v, id, &x, &y, &sl, &pl);
                 if (x >= P.width || y >= P.height || sl >= v.ns) {
                     live = false;
@@ -365,6 +369,20 @@ __global__ __launch_bounds__(256, WAVES) void wf_bounce(const WfArgs *__restrict
                 stk.n = DEEP ? (int)*deep_count(v, P.depth, id) : (int)count;
                 if (EXT) stk.vb = v.att + id;
                 PT_BSTAMP(1)
+            }
+        }
+        // The first launch's wave is one 8x8 pixel block of one sample (slot_pixel), so its lanes share the block's
+        // cull mask (pt_cull.hpp): one scalar load per wave, through the constant address space (the table is written
+        // before the frame's chunks fork and never during them).  Lane 0 holds the block's top-left pixel: a block
+        // outside the frame has no live lane and needs no mask.
+        uint64_t cull_mask = ~0ull;
+        if (FIRST && !SPLIT) {
+            if (const uint64_t *tab = v.cull) {
+                const uint32_t bx = __builtin_amdgcn_readfirstlane(x / cull::BLOCK);
+                const uint32_t by = __builtin_amdgcn_readfirstlane(y / cull::BLOCK);
+                const uint32_t nbx = cull::blocks_across(P.width), nby = cull::blocks_across(P.height);
+                typedef const __attribute__((address_space(4))) uint64_t *ctab;
+                if (bx < nbx && by < nby) cull_mask = ((ctab)tab)[(size_t)by * nbx + bx];
             }
         }
         // One bounce of this path: shade the pending hit (the camera ray has
@@ -404,11 +422,15 @@ __global__ __launch_bounds__(256, WAVES) void wf_bounce(const WfArgs *__restrict
             // miss matters (any hit gives black), so a path with a hit found
             // needs no march either
             const bool any = depth == 0;
-            dev::closest_nomarch<false, EXT, BIGBVH>(kargs(A).sc, ray, inv, T_MIN, &best, &who, nullptr, any);
+            // (FIRST: without the list entries no camera ray of this wave's pixel block can reach)
+            dev::closest_nomarch<false, EXT, BIGBVH, false, 3, FIRST>(kargs(A).sc, ray, inv, T_MIN, &best, &who, nullptr,
+                                                                     any, cull_mask);
             PT_BSTAMP(4)
             // does any marched shape's bound start before the best hit? (the
             // march kernel marches it)
             for (int k = 0; k < sc.nmarch && !need_march && !(any && who >= 0); k++) {
+                // (FIRST: a marched shape whose box the block's rays all miss fails the slab test below)
+                if (FIRST && k < 64 - cull::LIST_BITS && !((cull_mask >> (cull::LIST_BITS + k)) & 1ull)) continue;
                 const int s = dev::uniform_index(dev::uniform_load(&sc.march[k]));
                 const DBox bx = dev::uniform_box(&sc.boxes[s]);
                 if (!dev::slab(bx.lo, bx.hi, ray, inv, T_MIN, best)) continue;
@@ -478,7 +500,7 @@ __global__ __launch_bounds__(256, WAVES) void wf_bounce(const WfArgs *__restrict
         PT_BSTAMP(6)
     }
 #undef PT_BSTAMP
-    PT_LP_END();
+    PT_LP_END(it);
     if (DIAG && (threadIdx.x & 63) == 0)
         for (int k = 0; k < 7; k++) atomicAdd(&diag[36 + k], dsec[k]);
 }
@@ -1175,12 +1197,18 @@ static void release_streams(WaveWorkspace *ws) {
     ws->used = false;
 }
 
+static void free_cull(WaveWorkspace *ws) {
+    if (ws->first_cull.table) (void)hipFree(ws->first_cull.table);
+    ws->first_cull = WaveWorkspace::FirstCull{};
+}
+
 void wave_workspace_free(WaveWorkspace *ws) {
     release_streams(ws);
     timer_free(ws->timer);
     ws->timer = nullptr;
     if (ws->diag) (void)hipFree(ws->diag);
     ws->diag = nullptr;
+    free_cull(ws);
     if (ws->base) (void)hipFree(ws->base);
     ws->base = nullptr;
     ws->bytes = 0;
@@ -1339,6 +1367,7 @@ static hipError_t ensure_streams(WaveWorkspace *ws, int slots) {
         // the previous frame must be done with the streams and the workspace
         if (ws->used && ws->done && (e = hipEventSynchronize(ws->done)) != hipSuccess) return e;
         release_streams(ws);  // (the argument blocks live on the old device too)
+        free_cull(ws);        // (and so does the cull table)
         ws->device = dev;
     }
     if (!ws->fork && (e = hipEventCreateWithFlags(&ws->fork, hipEventDisableTiming)) != hipSuccess) return e;
@@ -1362,12 +1391,85 @@ struct Slot {
 // Slot j's stream: the caller's, then the side streams.
 static hipStream_t slot_stream(const WaveWorkspace *ws, hipStream_t st, int j) { return j == 0 ? st : ws->side[j - 1]; }
 
+// The frame's cull table, one thread per pixel block (on the host the 1080p table's 9M dot products take
+// milliseconds, too long for a camera that moves every frame).
+static __global__ __launch_bounds__(256) void wf_cull_table(FrameParams P, const int32_t *__restrict__ lin, int nlin,
+                                                            const int32_t *__restrict__ march, int nmarch,
+                                                            const DBox *__restrict__ boxes, uint32_t nbx, uint32_t nby,
+                                                            uint64_t *__restrict__ table) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nbx * nby) return;
+    table[b] = cull::first_cull_mask(P, lin, nlin, march, nmarch, boxes, b % nbx, b / nbx);
+}
+
+// The table for this frame's first bounce launch, queued on st (after the previous frame, before the chunks' streams
+// fork): kept when the frame's caster, size and acceleration data are those it was made for, so a frame with an
+// unchanged camera pays one host compare.  Returns null for a frame that has no use for it.
+static hipError_t first_cull_table(WaveWorkspace *ws, const dev::Scene &sc, uint64_t accel_gen, const FrameParams &P,
+                                   const builds::Choice &bc, hipStream_t st, const uint64_t **table) {
+    *table = nullptr;
+    // the first launch traces (no SPLIT build: wf_walk traces those), and there is something to cull
+    if (bc.bounce.split || (sc.nlin == 0 && sc.nmarch == 0)) return hipSuccess;
+    WaveWorkspace::FirstCull &fc = ws->first_cull;
+    const cull::CasterKey key = cull::caster_key(P);
+    const uint32_t nbx = cull::blocks_across(P.width), nby = cull::blocks_across(P.height);
+    const size_t blocks = (size_t)nbx * nby;
+    if (blocks == 0 || blocks > 0xffffffffu) return hipSuccess;
+    fc.used = true;
+    *table = fc.table;
+    if (fc.valid && fc.accel_gen == accel_gen && fc.boxes == sc.boxes && fc.blocks == blocks &&
+        !memcmp(&fc.key, &key, sizeof key))
+        return hipSuccess;
+    fc.valid = false;
+    hipError_t e;
+    if (blocks > fc.cap) {
+        // (the previous frame, which may still read the old buffer, is done: the caller waited for ws->done on st,
+        // and hipFree waits for the device)
+        if (fc.table) (void)hipFree(fc.table);
+        fc.table = nullptr;
+        fc.cap = 0;
+        *table = nullptr;
+        if ((e = hipMalloc((void **)&fc.table, blocks * sizeof(uint64_t))) != hipSuccess) {
+            fc.table = nullptr;
+            fc.used = false;
+            return e;
+        }
+        fc.cap = blocks;
+    }
+    wf_cull_table<<<(uint32_t)((blocks + 255) / 256), 256, 0, st>>>(P, sc.lin, sc.nlin, sc.march, sc.nmarch, sc.boxes,
+                                                                    nbx, nby, fc.table);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    fc.key = key;
+    fc.accel_gen = accel_gen;
+    fc.boxes = sc.boxes;
+    fc.blocks = blocks;
+    fc.valid = true;
+    *table = fc.table;
+    return hipSuccess;
+}
+
+// The set bits over the table the last launch_render call's frame read (-1: it read none), after that frame.
+hipError_t first_cull_bits(const WaveWorkspace &ws, int64_t *bits) {
+    *bits = -1;
+    const WaveWorkspace::FirstCull &fc = ws.first_cull;
+    if (!fc.used || !fc.valid || !fc.table) return hipSuccess;
+    hipError_t e;
+    if (ws.used && (e = hipEventSynchronize(ws.done)) != hipSuccess) return e;
+    std::vector<uint64_t> h(fc.blocks);
+    if ((e = hipMemcpy(h.data(), fc.table, fc.blocks * sizeof(uint64_t), hipMemcpyDeviceToHost)) != hipSuccess) return e;
+    int64_t n = 0;
+    for (uint64_t m : h) n += __builtin_popcountll(m);
+    *bits = n;
+    return hipSuccess;
+}
+
 // Queues this rank's tiles of the frame (of a resumable frame: the window [s_begin, s_end) of its samples) on st:
 // the plan (pt_plan.hpp), the workspace, the chunks' argument blocks, then the chunks step by step, with the kernel
 // builds of `bc` (builds::choose, pt_builds.hpp).  tiles (host, P0.tile_count entries, P0.tile_begin 0; null: none):
 // a listed launch, whose position g is entry tiles[g] of the rank's list (WfView::tile_map); copied before returning.
+// accel_gen: DeviceScene::accel_gen of sc's acceleration part.
 hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, double *out, hipStream_t st,
-                              WaveWorkspace *ws, const builds::Choice &bc, const uint32_t *tiles) {
+                              WaveWorkspace *ws, const builds::Choice &bc, const uint32_t *tiles, uint64_t accel_gen) {
     if (P0.tile_count == 0 || P0.spp == 0) return hipSuccess;
     const Tuning &tu = ws->tune;
     plan::Input in;
@@ -1420,6 +1522,9 @@ hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
     // render_device): this frame's kernels wait for the previous frame's.
     if (ws->used && (e = hipStreamWaitEvent(st, ws->done, 0)) != hipSuccess) return e;
     if ((e = reserve(ws, pl.bytes)) != hipSuccess) return e;
+    // the first launch's cull table: remade here, on st, when the camera, the size or the acceleration data moved
+    const uint64_t *cull_table = nullptr;
+    if ((e = first_cull_table(ws, sc, accel_gen, P0, bc, st, &cull_table)) != hipSuccess) return e;
     // the slots' path state and the running sums they share, where the layout puts them
     Slot sl[WaveWorkspace::MAX_SLOTS];
     for (int k = 0; k < slots; k++) {
@@ -1465,6 +1570,7 @@ hipError_t launch_render_wave(const dev::Scene &sc, const FrameParams &P0, doubl
         WfView v = sl[j].v;
         v.tile0 = P0.tile_begin + ch.g0;
         v.tile_map = tile_map;
+        v.cull = cull_table;
         v.npix = ch.gt * TILE * TILE;
         v.s0 = ch.s0;
         v.ns = ch.ns;

@@ -5,6 +5,11 @@ Needs a build with -DPT_LANE_PROF (scripts/variants.sh lprof "-DPT_LANE_PROF"), 
 a point inside a loop counts one pass per trip.
 
     PT_AMD_LIB=variants/lprof.so python scripts/bounce_lanes.py [spp] [scene] [width height]
+
+One bounce iteration alone: a build with -DPT_LANE_PROF_IT=n beside -DPT_LANE_PROF counts only the launches of
+iteration n (n = 0: the camera rays' launch, wf_bounce<FIRST>); name it here with PT_LANE_PROF_IT=n in the
+environment, so that the header says what was counted (the per-1000-paths columns are then per 1000 paths of that
+iteration).
 """
 import ctypes as C
 import os
@@ -49,8 +54,10 @@ r.render_device(cam, W, H, spp, 1, 0, 1, frame.data_ptr(), 0)
 torch.cuda.synchronize()
 f(buf, 0)
 live_lanes = buf[n + 0]
-print("bounce kernel lane profile: %s %dx%d %d spp, one chunk stream; %d live path-bounces (%.2f per sample)"
-      % (scene, W, H, spp, live_lanes, live_lanes / (W * H * spp)))
+only = os.environ.get("PT_LANE_PROF_IT")
+print("bounce kernel lane profile: %s %dx%d %d spp, one chunk stream%s; %d live path-bounces (%.2f per sample)"
+      % (scene, W, H, spp, ", bounce iteration %s alone" % only if only else "", live_lanes,
+         live_lanes / (W * H * spp)))
 print("  %-12s %14s %8s %16s %18s" % ("point", "wave passes", "lanes", "passes/1k paths", "lane-passes/1k"))
 for k, name in enumerate(NAMES):
     w, l = buf[k], buf[n + k]
