@@ -22,6 +22,19 @@ extern "C" int march_heart(double step, int passes, const double *inv /*3x4 row-
     return hit;
 }
 
+// shape_mag (pt_funcs.hpp): the sign proof's magnitude bound of one function and of its gradient over the box
+// |x| <= xm, |y| <= ym, |z| <= zm.  k: FParams::k as the loader fills it.  out = {v, gx, gy, gz}.
+extern "C" void shape_mag_of(int func, const double *k, double xm, double ym, double zm, double *out) {
+    pt::march::FParams F{};
+    F.func = func;
+    for (int i = 0; i < 4; i++) F.k[i] = k[i];
+    const pt::march::DM m = pt::march::shape_mag(F, xm, ym, zm);
+    out[0] = m.v;
+    out[1] = m.gx;
+    out[2] = m.gy;
+    out[3] = m.gz;
+}
+
 // lin_room (the straight-line form the kernels use) against lin_init (the
 // branchy original) on n pseudo-random (x, c) pairs: the same room and the
 // same (X, R, u) wherever lin_init's room is >= 2, a room < 2 elsewhere.

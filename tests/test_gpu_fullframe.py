@@ -119,17 +119,8 @@ def test_c1_full_frame_every_pixel(pt, spheres_text):
 
 
 def _compare_hits(got, osc, rays):
-    bad = []
-    for i, ray in enumerate(rays):
-        hh = osc.closest_hit(ray[:3], ray[3:])
-        g = got[i]
-        if hh is None:
-            ok = g["shape"] == -1
-        else:
-            ok = (g["shape"] == hh.shape and g["t"] == hh.t and list(g["normal"]) == list(hh.normal))
-        if not ok:
-            bad.append(i)
-    return bad
+    """Indices of the rays whose hit (shape, t, point, normal, front face; NaN equal to NaN) is not the oracle's."""
+    return A.hit_differences(A.gpu_hit_records(got), A.oracle_hit_records(osc, rays))
 
 
 @pytest.mark.parametrize("xf,step,depth", [
